@@ -22,15 +22,22 @@ with --envs); config5 (640 x 640 cells, 640 rays, 100 agents) runs the closed lo
 its fused Drone2DEnv2.step alone (NoMove, fixed-seed gaze actions: the figure of rounds 1 and 2).  The BASELINE jobs of 262144
 envs are `--workload config4 --gpus 8` and `--workload config5 --gpus 8` (32768 envs per GPU).
 
-Besides the headline the line carries, measured after the timed region with HIP events on the launch stream:
+A plain run does only what the headline needs: worlds, prologue, warm-up, the timed steps, the line (with `roofline` / `valu`
+of the timed launches, from the PMC file below).  `--full` adds, measured after the timed region with HIP events on the
+launch stream:
   step_kernel    the fused Drone2DEnv2.step kernel alone (k_stages; actions and planner heads resident in HBM)
   raycast_stage  d2d_run_stages(AGENTS | RAYCAST): the raycast kernel the north star's HBM target is quoted on
 (--leg picks one of them for a profiler run: every k_stages row of that trace is then that leg), and `large_batch`:
 the closed loop, the step kernel and the raycast stage once more on 65 536 envs (--large; the workload's worlds tiled),
-where launch ramp and the tail of slow envs are amortised -- the throughput regime of the same kernels.
+where launch ramp and the tail of slow envs are amortised -- the throughput regime of the same kernels, and `cpu_baseline`
+(the CPU oracle on a sample of the same workload).
 PMC-derived fields (`traffic`, `valu`) come from profiles/pmc_latest.json, which stores them PER ENV-STEP together
 with the launch shape they were measured on; they are scaled to this run's launch and emitted only when workload,
 envs and launch mode match the profile (else null), with `traffic_source` naming the file.
+
+--dump-outputs DIR writes what the timed path returned for its last step (closed_loop()'s obs / reward / done / info, of rank
+0's shard) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: above that, a fixed seeded sample of envs (the rows
+kept in DIR/env_index.npy).  The inputs depend on the arguments only, so two builds can be compared file by file.
 
 N>1: every rank runs its own shard (weak scaling, no per-step collective; one RCCL all_gather of episode statistics,
 timed separately as `gather_ms`).  Prints ONE JSON line on rank 0.
@@ -155,6 +162,34 @@ def cpu_baseline(pkg, params, closed, budget_s=16.0):
             'sample': f'oracle/d2d_oracle.c {loop}, {B} envs x {env.N} agents ({nw} distinct seeded worlds of the GPU '
                       f'workload\'s family), ~{budget_s / 2:.0f} s per thread count {sorted(out)}; reference Python itself: '
                       '16.3 env-steps/s for the config-2 closed loop on 1 core (BASELINE.md, build container)'}
+
+
+DUMP_LIMIT = 64 << 20               # bytes of --dump-outputs
+
+
+def dump_outputs(out_dir, result, seed=20240):
+    """Write the (obs, reward, done, info) of a step as out_dir/<name>.npy: float32 for 8 / 16-bit integers, bools and
+    float32, float64 for wider integers and float64 (every value exact).  Above DUMP_LIMIT bytes a fixed, seeded sample of envs
+    (the same rows of every array) is written, with their indices in env_index.npy."""
+    import numpy as np
+    obs, reward, done, info = result
+    named = [('obs_' + k, v) for k, v in obs.items()] + [('reward', reward), ('done', done)] + [('info_' + k, v) for k, v in info.items()]
+    arrays = {}
+    for name, v in named:
+        a = v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+        wide = a.dtype == np.float64 or (a.dtype.kind in 'iu' and a.dtype.itemsize > 2)
+        arrays[name] = np.ascontiguousarray(a, dtype=np.float64 if wide else np.float32)
+    B = len(arrays['reward'])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        keep = min(B, int(DUMP_LIMIT // (total / B + 8)))
+        idx = np.sort(np.random.RandomState(seed).choice(B, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays['env_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sum(a.nbytes for a in arrays.values())
 
 
 class Clock:
@@ -501,19 +536,28 @@ def main():
     ap.add_argument('--no-persistent', action='store_true',
                     help='exploration: one launch per stage per step (gaze, perceive, plan, act) instead of the persistent kernel')
     ap.add_argument('--large', type=int, default=65536,
-                    help='envs of the large-batch legs reported beside the headline (the same kernels where launch ramp and the tail '
-                         'of slow envs are amortised: the throughput regime); 0 = skip')
+                    help='envs of the large-batch legs reported beside the headline with --full (the same kernels where launch ramp '
+                         'and the tail of slow envs are amortised: the throughput regime); 0 = skip')
     ap.add_argument('--grid-layout', default=None, choices=['rowmajor', 'tiled'],
                     help='device layout of the two grids (default: the library\'s choice -- 16 x 16-cell tiles above 256 x 256 cells)')
     ap.add_argument('--distinct-worlds', type=int, default=0,
                     help='build only this many seeded worlds per rank and tile them over the batch (0 = one world per env)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also measure the step_kernel and raycast_stage legs, the large_batch legs and the '
+                         'cpu_baseline (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path returned for its last step to DIR/<name>.npy (float32 / float64, <= 64 MB)')
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.dump_outputs and args.leg not in ('all', 'closed'):
+        ap.error('--dump-outputs needs the timed region (--leg all or closed)')
     if args.workload == 'survivability':
         if args.gpus != 1:
             ap.error('--workload survivability is a one-GPU job')
+        if args.dump_outputs:
+            ap.error('--dump-outputs: the step workloads only')
         sys.exit(survivability_bench(args))
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process only starts the N ranks (nothing here has touched the GPU)
@@ -571,10 +615,11 @@ def main():
     shape = {'workload': args.workload, 'envs': B, 'persistent': bool(closed and not args.no_persistent)}
     nlaunch_of = lambda n: (n + args.chunk - 1) // args.chunk if closed else n
 
+    last = [None]                           # what the last call of the timed path returned (--dump-outputs)
     if closed:
         def run(n):
             for c0 in range(0, n, args.chunk):
-                env.closed_loop(min(args.chunk, n - c0), auto_reset=True)
+                last[0] = env.closed_loop(min(args.chunk, n - c0), auto_reset=True)
     else:
         g = torch.Generator().manual_seed(4321 + rank)
         T = args.prologue + Wm + K
@@ -609,6 +654,8 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
         nlaunch = nlaunch_of(K)
+        if args.dump_outputs and rank == 0:     # before any leg below touches `env`
+            dump_outputs(args.dump_outputs, last[0] if closed else env._result())
 
         # episode statistics: the only exchange of the path (RCCL all_gather over xGMI), once per run
         stats = env.episode_stats()
@@ -669,7 +716,7 @@ def main():
 
     if rank == 0:
         sshape = {'workload': args.workload, 'envs': B}
-        if args.leg in ('all', 'step'):       # after the timed region, on its own state
+        if args.leg == 'step' or (args.leg == 'all' and args.full):       # after the timed region, on its own state
             env_hot = vec_env.VecDrone2DEnv(params, B, device=device, planner='external' if closed else 'NoMove',
                                             env_offset=rank * B, worlds=worlds, grid_layout=args.grid_layout)
             us, reps = stage_leg(torch, clock, env_hot, params, rank, B, 'step')
@@ -679,7 +726,7 @@ def main():
                 'launches': 500, 'repetitions_us': reps, 'env_steps_per_s': B / (us * 1e-6),
                 'roofline': roofline('k_stages', sshape, algo, B, 1, us), 'valu': valu('k_stages', sshape, B / (us * 1e-6))}
             del env_hot
-        if args.leg in ('all', 'raycast'):
+        if args.leg == 'raycast' or (args.leg == 'all' and args.full):
             # the raycast stage on mid-episode worlds: after the timed region on the closed-loop state, else after a short flight
             if args.leg == 'raycast':
                 run(min(args.prologue, 100))
@@ -692,9 +739,9 @@ def main():
                 'roofline': roofline('raycast_stage', sshape, rb, B, 1, us,
                                      {'note': 'bytes: 36 N agents + N hit mask + R S ground-truth reads + R (S - 1) drone-map writes + 44 B pose'}),
                 'valu': valu('raycast_stage', sshape, B / (us * 1e-6))}
-        if args.large and world == 1 and args.leg == 'all' and closed and use_cuda:
+        if args.full and args.large and world == 1 and args.leg == 'all' and closed and use_cuda:
             line['large_batch'] = large_batch_legs(torch, clock, pkg, vec_env, params, worlds, rank, args.large, args.chunk, args.workload)
-        if not args.no_cpu_baseline and world == 1 and args.leg == 'all':
+        if args.full and not args.no_cpu_baseline and world == 1 and args.leg == 'all':
             line['cpu_baseline'] = cpu_baseline(pkg, params, closed)
         print(json.dumps(line), flush=True)
     if world > 1:

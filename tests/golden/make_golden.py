@@ -312,8 +312,9 @@ def gen_closed():
 
 
 def gen_live(outdir, seed0, count, wide=False, scale20=False):
-    """Random closed-loop Oxford + Primitive episodes of the live reference into `outdir` (not committed: the
-    build-container-only test tests/test_oracle_vs_live_reference.py replays them through the oracle)."""
+    """Random closed-loop Oxford + Primitive episodes of the live reference into `outdir` (an absolute path: the script runs in
+    the reference's directory).  tests/test_oracle_vs_live_reference.py replays the committed ones (`live <tests/golden> 4242 8`
+    and `live <tests/golden> 9100 6 wide`) through the oracle."""
     global OUT
     OUT = outdir
     for k in range(count):
@@ -394,7 +395,86 @@ def gen_cfg5_closed():
     save('closed_oxford_cfg5_640', run_trace(p, 45, policy='Oxford'))
 
 
+def gen_gaze_values():
+    """yaw_planner.LookAhead / LookGoal .plan() on 4000 random observations (drones at rest, the +-180 degree wrap, yaw outside
+    [0, 360), empty trajectories, trajectories through explored / unexplored / out-of-map cells).  The observations are
+    regenerated from the same seed by tests/test_dropin_reference_plugins.py::test_host_gaze_policies_equal_the_reference_classes,
+    in the same order of draws."""
+    P = types.SimpleNamespace(dt=0.1, drone_max_yaw_speed=80)
+    rng = np.random.RandomState(11)
+
+    class Map:
+        def __init__(self, g):
+            self.g = g
+
+        def get_grid(self, x, y):
+            if x >= 500 or x < 0 or y >= 500 or y < 0:
+                return 1
+            return self.g[int(x // 10), int(y // 10)]
+
+    class Traj:
+        def __init__(self, pts):
+            self.positions = pts
+
+        def __len__(self):
+            return len(self.positions)
+
+    vals = np.zeros((4000, 2), dtype=np.float64)
+    for case in range(4000):
+        vel = rng.uniform(-40, 40, 2) * rng.choice([0, 1, 1, 1], 2)
+        if case % 7 == 0:
+            vel = np.round(vel)
+        yaw = rng.uniform(-400, 800) if case % 3 else float(rng.randint(0, 360))
+        drone = types.SimpleNamespace(velocity=vel, yaw=yaw, x=float(rng.randint(0, 500)), y=float(rng.randint(0, 500)),
+                                      map=Map(rng.choice([0, 1, 2], (50, 50), p=[0.2, 0.1, 0.7]).astype(np.uint8)))
+        pts = [np.round(rng.uniform(-20, 520, 2)) for _ in range(rng.randint(0, 12))]
+        if case % 11 == 0 and pts:
+            pts[-1] = np.array([drone.x, drone.y])                     # atan2(-0.0, 0.0)
+        obs = {'drone': drone, 'trajectory': Traj(pts), 'target': np.array([250., 250.])}
+        for j, name in enumerate(('LookAhead', 'LookGoal')):
+            vals[case, j] = np.float64(getattr(yaw_planner, name)(P).plan(obs))
+    save('host_gaze_values', dict(values=vals, names=np.array(['LookAhead', 'LookGoal'])))
+
+
+def gen_facade_noise():
+    """var_cam = 2 on the reference env: the drone is put next to an agent every tenth step, the actions are U(-1, 1) of
+    RandomState(5).  Per step: the pose put (or -1), the action, the trackers' active bits, last updated means and
+    covariances, the ground-truth grid and tracked_agent (tests/test_dropin_reference_plugins.py::
+    test_measurement_noise_through_the_facade steps the package's facade through the same inputs)."""
+    kw = dict(planner='NoMove', gaze_method='NoControl', agent_number=14, agent_radius=14, agent_max_speed=20, map_id=77,
+              var_cam=2, init_pos=[250, 250])
+    ref = Drone2DEnv2(make_params(**kw))
+    N = len(ref.agents)
+    rng = np.random.RandomState(5)
+    rec = {k: [] for k in ('tele', 'action', 'active', 'mu', 'sigma', 'gt', 'tracked')}
+    for t in range(60):
+        pos = (-1, -1)
+        if t % 10 == 0:
+            a = ref.agents[(3 * t // 10) % N].position
+            x, y = int(a[0]) + 10, int(a[1]) - 45
+            pos = (min(max(x, 30), 470), min(max(y, 30), 470))
+            ref.drone.x, ref.drone.y = pos
+        act = float(rng.uniform(-1, 1))
+        ref.step(act)
+        trs = ref.drone.trackers[:N]
+        rec['tele'].append(pos)
+        rec['action'].append(act)
+        rec['active'].append([bool(tr.active) for tr in trs])
+        rec['mu'].append([np.asarray(tr.mu_upds[-1], dtype=np.float64)[:, 0] if tr.active else np.full(4, np.nan) for tr in trs])
+        rec['sigma'].append([np.asarray(tr.Sigma_upds[-1], dtype=np.float64) if tr.active else np.full((4, 4), np.nan) for tr in trs])
+        rec['gt'].append(ref.map_gt.grid_map.copy())
+        rec['tracked'].append(ref.tracked_agent)
+    d = {k: np.array(v) for k, v in rec.items()}
+    d['tele'] = d['tele'].astype(np.int64)
+    d['cfg'] = np.array(json.dumps(kw))
+    save('facade_noise_var_cam2', d)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'gaze_values':
+        return gen_gaze_values()
+    if len(sys.argv) > 1 and sys.argv[1] == 'facade_noise':
+        return gen_facade_noise()
     if len(sys.argv) > 1 and sys.argv[1] == 'cfg5closed':
         return gen_cfg5_closed()
     if len(sys.argv) > 1 and sys.argv[1] == 'cfg5':
@@ -506,6 +586,8 @@ def main():
     gen_host_gaze()
     gen_flags()
     gen_closed()
+    gen_gaze_values()
+    gen_facade_noise()
 
 
 if __name__ == '__main__':

@@ -215,3 +215,85 @@ def test_bench_survivability_workload_dry_run():
     j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
     assert j['config']['table_shape'] == [27, 8, 8, 240] and j['value'] > 0 and j['cpu_baseline']['table_of_map_0_equals_oracle']
     assert [r['agents'] for r in j['roofline']['per_agent_count']] == [10, 20, 30] and j['roofline']['frac'] > 0
+
+
+def _bench_line(out):
+    import json
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_the_timed_path_outputs(pkg, oracle, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (CPU dry run): the line of the headline alone (no step / raycast
+    / large-batch legs, no cpu_baseline: those are --full), ms_per_step of exactly K timed steps, and DIR/*.npy = what the last
+    closed_loop() call returned -- the same from run to run, and equal to the oracle's own env after prologue + W + K steps."""
+    import subprocess
+    from drone2d_amd import vec_env
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    env['OMP_NUM_THREADS'] = '1'
+    lines = []
+    for d in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(ROOT, 'tests', 'bench_dry_rank.py'), '--gpus', '1', '--steps', '3', '--warmup', '2',
+               '--prologue', '2', '--envs', '5', '--workers', '0', '--dump-outputs', str(tmp_path / d)]
+        lines.append(_bench_line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)))
+    j = lines[0]
+    assert j['steps'] == 3 and j['warmup'] == 2 and j['n_gpus'] == 1 and j['value'] > 0
+    assert abs(j['value'] - 5 * 1e3 / j['ms_per_step']) < 1e-6 * j['value']
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline'):
+        assert k in j, k
+    for k in ('step_kernel', 'raycast_stage', 'large_batch', 'cpu_baseline'):
+        assert k not in j, k
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) and 'reward.npy' in names and 'obs_local_map.npy' in names
+    got = {n[:-4]: np.load(tmp_path / 'a' / n) for n in names}
+    for n, a in got.items():
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(tmp_path / 'b' / (n + '.npy'))), n
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    p = pkg.Params(planner='Primitive', gaze_method='Oxford', drone_max_speed=40, map_id=1, agent_number=10, agent_radius=15,
+                   agent_max_speed=20)
+    ref = vec_env.VecDrone2DEnv(p, 5, backend=oracle, planner='Primitive', device_plugins=True, gaze='Oxford')
+    for n in (2, 2, 3):                                   # prologue, warm-up, timed steps
+        obs, reward, done, info = ref.closed_loop(n, auto_reset=True)
+    want = dict({'obs_' + k: v for k, v in obs.items()}, reward=reward, done=done, **{'info_' + k: v for k, v in info.items()})
+    assert sorted(want) == sorted(got)
+    for k, v in want.items():
+        assert np.array_equal(got[k], v.numpy().astype(got[k].dtype)), k
+
+
+def test_bench_full_run_adds_the_legs():
+    """--full (CPU dry run): the step_kernel and raycast_stage legs after the headline, as a plain run had them before."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
+    env['OMP_NUM_THREADS'] = '1'
+    cmd = [sys.executable, os.path.join(ROOT, 'tests', 'bench_dry_rank.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+           '--prologue', '1', '--envs', '2', '--workers', '0', '--full', '--large', '0', '--no-cpu-baseline']
+    j = _bench_line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT))
+    assert j['steps'] == 2 and j['value'] > 0
+    assert j['step_kernel']['env_steps_per_s'] > 0 and j['raycast_stage']['env_steps_per_s'] > 0
+
+
+def test_bench_dump_outputs_samples_above_the_limit(tmp_path, monkeypatch):
+    """Above the byte limit --dump-outputs writes a fixed, seeded sample of envs (the same rows of every array, indices in
+    env_index.npy), under the limit."""
+    import runpy
+    import torch
+    bench = runpy.run_path(os.path.join(ROOT, 'bench.py'), run_name='bench')
+    B = 64
+    obs = {'local_map': torch.arange(B * 9, dtype=torch.uint8).reshape(B, 1, 3, 3), 'yaw_angle': torch.rand(B, 1, dtype=torch.float64)}
+    info = {'steps': torch.arange(B, dtype=torch.int32)}
+    result = (obs, torch.rand(B, dtype=torch.float32), torch.zeros(B, dtype=torch.bool), info)
+    fn = bench['dump_outputs']
+    fn.__globals__['DUMP_LIMIT'] = 1000
+    try:
+        for d in ('a', 'b'):
+            assert fn(str(tmp_path / d), result) <= 1000
+    finally:
+        fn.__globals__['DUMP_LIMIT'] = 64 << 20
+    idx = np.load(tmp_path / 'a' / 'env_index.npy').astype(np.int64)
+    assert 0 < len(idx) < B and np.array_equal(idx, np.load(tmp_path / 'b' / 'env_index.npy'))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'info_steps.npy'), idx.astype(np.float64))
+    assert np.load(tmp_path / 'a' / 'info_steps.npy').dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / 'a' / 'obs_local_map.npy'), obs['local_map'].numpy()[idx].astype(np.float32))

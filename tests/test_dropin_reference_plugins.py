@@ -1,211 +1,23 @@
-"""Drop-in check of the plugin surface with the REFERENCE'S OWN planner and gaze classes (only where the reference
-checkout exists, i.e. in the build container; skipped on the GPU box): `traj_planner.Primitive` and
-`yaw_planner.Oxford`, imported from /root/reference, drive this repo's env through its proxies and reproduce the
-reference episode."""
-import os
-import sys
+"""The plugin surface against what the reference's own classes and env computed (fixtures written by
+tests/golden/make_golden.py from the reference): the package's host gaze policies against yaw_planner.LookAhead /
+LookGoal on random observations, and the facade's measurement-noise path against the reference env with var_cam = 2."""
+import json
 import types
 
 import numpy as np
-import pytest
 
-from replay import load, params_from
-
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present')
+from replay import load
 
 
-@pytest.fixture(scope='module')
-def ref_modules():
-    def mk(n):
-        m = types.ModuleType(n)
-        sys.modules[n] = m
-        return m
-    saved = {k: sys.modules.get(k) for k in ('pygame', 'cvxpy', 'cvxpy.error', 'gym', 'gym.spaces', 'gym.envs',
-                                             'gym.envs.registration', 'utils', 'traj_planner', 'yaw_planner')}
-    mk('pygame')
-    cv = mk('cvxpy'); ce = mk('cvxpy.error'); ce.SolverError = Exception; cv.error = ce
-    if 'gym' not in sys.modules or sys.modules['gym'] is None:
-        gym = mk('gym'); gym.__path__ = []
-        gym.Env = type('Env', (), {})
-        gym.logger = type('L', (), {'set_level': staticmethod(lambda x: None)})
-        sp = mk('gym.spaces'); sp.Box = type('Box', (), {'__init__': lambda s, *a, **k: None}); sp.Dict = type('Dict', (), {'__init__': lambda s, d: None})
-        gym.spaces = sp
-        ge = mk('gym.envs'); ge.__path__ = []
-        gr = mk('gym.envs.registration'); gr.register = lambda **k: None
-        ge.registration = gr; gym.envs = ge
-    import matplotlib
-    matplotlib.use('Agg')
-    sys.path.insert(0, REF)
-    cwd = os.getcwd()
-    os.chdir(REF)
-    try:
-        import traj_planner
-        import yaw_planner
-        yield traj_planner, yaw_planner
-    finally:
-        os.chdir(cwd)
-        sys.path.remove(REF)
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-
-
-def test_reference_primitive_and_oxford_drive_this_env(pkg, oracle, ref_modules):
-    traj_planner, yaw_planner = ref_modules
-    from drone2d_amd import env as envmod, planners
-    fx = load('readme_oxford_primitive')
-    p = params_from(fx, pkg)
-    own = planners.planner_list['Primitive']
-    planners.register_planner('Primitive', traj_planner.Primitive)      # the reference's class, unmodified
-    try:
-        e = envmod.Drone2DEnv2(p, backend=oracle)
-        assert type(e.planner).__module__ == 'traj_planner' and e._mode == 'host'
-        pol = yaw_planner.Oxford
-        pol.__init__(pol, p)
-        done, t = False, 0
-        while not done and t < 400:
-            a = pol.plan(pol, e.info)
-            assert abs(float(a) - fx['t_action'][t]) <= 1e-12
-            obs, rew, done, info = e.step(a)
-            d = fx['t_drone'][t]
-            assert (e.drone.x, e.drone.y) == (d[0], d[1]) and np.array_equal(obs['local_map'][0], fx['t_obs_local'][t])
-            t += 1
-        assert t == 210 and info['state_machine'] == 1 and (e.drone.x, e.drone.y) == (42, 455)
-    finally:
-        planners.register_planner('Primitive', own)
-
-
-def test_reference_experiment_driver_runs_unchanged(pkg, oracle, ref_modules):
-    """experiment.py of the reference (its Experiment class, unmodified) on this env: gym.make is pointed at
-    Drone2DEnv2, as the one-line registration change of INTEGRATION.md does."""
-    import gym
-    from drone2d_amd import env as envmod
-    fx = load('lookahead_primitive_n30_map3')
-    p = params_from(fx, pkg)
-    gym.make = lambda env_id, params=None: envmod.Drone2DEnv2(params, backend=oracle)
-    saved_path = list(sys.path)
-    sys.path.insert(0, REF)
-    cwd = os.getcwd()
-    os.chdir(REF)
-    try:
-        sys.modules.pop('experiment', None)
-        import experiment                       # the reference's driver module
-        ex = experiment.Experiment(p, '/tmp/unused.csv')
-        ex.run()
-        info = ex.env.info
-        assert ex.env.steps == len(fx['t_action']) and info['collision_flag'] == fx['t_flags'][-1][0]
-        assert np.array_equal(ex.env.drone.map.grid_map, fx['t_dmap'][-1])
-    finally:
-        os.chdir(cwd)
-        sys.path[:] = saved_path
-        sys.modules.pop('experiment', None)
-
-
-def test_reference_oxford_drives_the_device_planner(pkg, oracle, ref_modules):
-    """The drop-in case of INTEGRATION.md: the reference's experiment.py keeps its own yaw_planner.Oxford (a host
-    object) while gym.make builds this env, whose Primitive planner is the device stage.  The host policy reads the
-    device trajectory through info['trajectory'] and reproduces the reference episode."""
-    traj_planner, yaw_planner = ref_modules
-    from drone2d_amd import env as envmod
-    fx = load('readme_oxford_primitive')
-    p = params_from(fx, pkg)
-    e = envmod.Drone2DEnv2(p, backend=oracle)
-    assert e._mode == 'device'
-    pol = yaw_planner.Oxford
-    pol.__init__(pol, p)
-    done, t = False, 0
-    while not done and t < 400:
-        a = pol.plan(pol, e.info)
-        assert abs(float(a) - fx['t_action'][t]) <= 1e-12
-        obs, rew, done, info = e.step(a)
-        d = fx['t_drone'][t]
-        assert (e.drone.x, e.drone.y) == (d[0], d[1]) and len(info['trajectory']) == fx['t_traj_len'][t]
-        t += 1
-    assert t == 210 and info['state_machine'] == 1 and (e.drone.x, e.drone.y) == (42, 455)
-
-
-def test_readme_command_with_default_params(pkg, oracle, ref_modules, monkeypatch):
-    """`python main.py --gaze_method Oxford --planner Primitive` as written in the reference's README: Params come from
-    the reference's own parser with its DEFAULTS (render=True, utils.py:75-77,112), its Experiment (experiment.py,
-    unmodified) calls env.render() every step (experiment.py:105-106) -- a headless no-op here."""
-    import warnings
-    import gym
-    from drone2d_amd import env as envmod
-    import utils as ref_utils                     # the reference's utils (on sys.path through the fixture)
-    monkeypatch.setattr(sys, 'argv', ['main.py', '--gaze_method', 'Oxford', '--planner', 'Primitive', '--map_id', '1',
-                                      '--agent_number', '10', '--agent_max_speed', '20', '--agent_radius', '15'])
-    cfg = ref_utils.Params.from_parser()
-    assert cfg.render is True and cfg.gaze_method == 'Oxford'
-    gym.make = lambda env_id, params=None: envmod.Drone2DEnv2(params, backend=oracle)
-    sys.modules.pop('experiment', None)
-    import experiment
-    try:
-        ex = experiment.Experiment(cfg, '/tmp/unused.csv')
-        with warnings.catch_warnings(record=True) as w:
-            warnings.simplefilter('always')
-            ex.run()
-        assert sum('headless' in str(x.message) for x in w) == 1
-        fx = load('readme_oxford_primitive')
-        assert ex.env.steps == 210 and (ex.env.drone.x, ex.env.drone.y) == (42, 455)
-        assert np.array_equal(ex.env.drone.map.grid_map, fx['t_dmap'][-1])
-    finally:
-        sys.modules.pop('experiment', None)
-
-
-def test_reference_lookahead_row(pkg, oracle, ref_modules):
-    """experiment_rows r1 (LookAhead + Primitive) with the REFERENCE'S LookAhead class registered over this package's:
-    the planner is the device stage, the CSV row is the reference's (tests/test_runner.py runs the same row with the
-    package's own LookAhead)."""
-    import json
-    from drone2d_amd import runner, gaze
-    fx = load('experiment_rows')
-    kw = json.loads(str(fx['r1_cfg']))
-    assert kw['gaze_method'] == 'LookAhead'
-    own = gaze.policy_list['LookAhead']
-    gaze.register_policy('LookAhead', ref_modules[1].LookAhead)
-    try:
-        p = pkg.Params(debug=True, **kw)
-        p.render = False
-        row = runner.Experiment(p, backend=oracle).run()
-    finally:
-        gaze.register_policy('LookAhead', own)
-    got = np.array([float(v) for v in row[12:]], dtype=np.float64)
-    assert np.allclose(got, fx['r1_row'], rtol=0, atol=1e-9, equal_nan=True), (got, fx['r1_row'])
-
-
-@pytest.mark.parametrize('case', [0, 3, 4])
-def test_reference_host_gaze_classes_on_this_env(pkg, oracle, ref_modules, case):
-    """The reference's own LookGoal / Owl classes, registered over this package's, read this env through its proxies
-    (trajectory view, map view, tracker views incl. inactive trackers) and reproduce the reference's episodes."""
-    import json
-    import warnings
-    from drone2d_amd import runner, gaze
-    fx = load('host_gaze_rows')
-    kw = json.loads(str(fx[f'r{case}_cfg']))
-    name = kw['gaze_method']
-    own = gaze.policy_list[name]
-    gaze.register_policy(name, getattr(ref_modules[1], name))
-    try:
-        p = pkg.Params(debug=True, **kw)
-        p.render = False
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore')
-            row = runner.Experiment(p, backend=oracle).run()
-    finally:
-        gaze.register_policy(name, own)
-    got = np.array([float(v) for v in row[12:]], dtype=np.float64)
-    assert np.allclose(got, fx[f'r{case}_row'], rtol=0, atol=1e-9, equal_nan=True), (got, fx[f'r{case}_row'])
-
-
-def test_host_gaze_policies_equal_the_reference_classes(pkg, ref_modules):
-    """gaze.LookAhead / gaze.LookGoal against yaw_planner.LookAhead / LookGoal on the same observations: same value,
-    bit for bit, over random states incl. a drone at rest, the +-180 degree wrap, yaw outside [0, 360), empty
-    trajectories and trajectories through explored / unexplored / out-of-map cells."""
+def test_host_gaze_policies_equal_the_reference_classes(pkg):
+    """gaze.LookAhead / gaze.LookGoal against yaw_planner.LookAhead / LookGoal on the same observations (golden
+    `host_gaze_values`, make_golden.py gaze_values: the same seed and order of draws): same value, bit for bit, over random
+    states incl. a drone at rest, the +-180 degree wrap, yaw outside [0, 360), empty trajectories and trajectories through
+    explored / unexplored / out-of-map cells."""
     from drone2d_amd import gaze
-    yp = ref_modules[1]
+    fx = load('host_gaze_values')
+    want = fx['values']
+    assert [str(n) for n in fx['names']] == ['LookAhead', 'LookGoal'] and want.shape == (4000, 2)
     P = types.SimpleNamespace(dt=0.1, drone_max_yaw_speed=80)
     rng = np.random.RandomState(11)
 
@@ -237,47 +49,34 @@ def test_host_gaze_policies_equal_the_reference_classes(pkg, ref_modules):
         if case % 11 == 0 and pts:
             pts[-1] = np.array([drone.x, drone.y])                     # atan2(-0.0, 0.0)
         obs = {'drone': drone, 'trajectory': Traj(pts), 'target': np.array([250., 250.])}
-        for name in ('LookAhead', 'LookGoal'):
-            mine, ref = getattr(gaze, name)(P), getattr(yp, name)(P)
-            a, b = mine.plan(obs), ref.plan(obs)
-            assert np.array_equal(np.float64(a), np.float64(b)) and np.signbit(a) == np.signbit(b), (name, case, a, b)
+        for j, name in enumerate(('LookAhead', 'LookGoal')):
+            a, b = getattr(gaze, name)(P).plan(obs), want[case, j]
+            assert np.array_equal(np.float64(a), b) and np.signbit(a) == np.signbit(b), (name, case, a, b)
             n += a != 0
     assert n > 3000
 
 
-def test_measurement_noise_through_the_facade(pkg, oracle, ref_modules):
+def test_measurement_noise_through_the_facade(pkg, oracle):
     """var_cam != 0: the reference draws np.random.randn(2) per agent the rays hit, in agent order, from the global stream it
     seeded with map_id (utils.py:603-605, envs/drone_v2.py:80).  The facade keeps that stream, splits the step after the raycast
-    and feeds the draws to the tracker stage: tracker means / covariances and active bits follow the LIVE reference env."""
-    import io
-    import contextlib
-    with contextlib.redirect_stdout(io.StringIO()):
-        from envs.drone_v2 import Drone2DEnv2 as RefEnv      # the reference's env (stubs for gym / pygame from the fixture)
-        import utils as ref_utils
+    and feeds the draws to the tracker stage: tracker means / covariances and active bits follow the reference env's (golden
+    `facade_noise_var_cam2`, make_golden.py facade_noise: the drone put next to an agent every tenth step, random actions)."""
     from drone2d_amd import env as envmod
-    kw = dict(planner='NoMove', gaze_method='NoControl', agent_number=14, agent_radius=14, agent_max_speed=20, map_id=77,
-              var_cam=2, init_pos=[250, 250])
-    rp = ref_utils.Params(debug=True, **kw)
-    rp.render = False
-    ref = RefEnv(rp)
+    fx = load('facade_noise_var_cam2')
+    kw = json.loads(str(fx['cfg']))
+    assert kw['var_cam'] == 2
     mine = envmod.Drone2DEnv2(pkg.Params(debug=True, **kw), backend=oracle)
-    rng = np.random.RandomState(5)
     seen = 0
-    for t in range(60):
-        if t % 10 == 0:                       # next to an agent, looking at it: rays hit, trackers start and update
-            a = ref.agents[(3 * t // 10) % len(ref.agents)].position
-            x, y = int(a[0]) + 10, int(a[1]) - 45
-            x, y = min(max(x, 30), 470), min(max(y, 30), 470)
-            ref.drone.x, ref.drone.y = x, y
+    for t in range(len(fx['action'])):
+        x, y = (int(v) for v in fx['tele'][t])
+        if x >= 0:                            # next to an agent, looking at it: rays hit, trackers start and update
             mine.drone.x, mine.drone.y = x, y
-        act = float(rng.uniform(-1, 1))
-        ref.step(act)
-        mine.step(act)
-        for k, tr in enumerate(ref.drone.trackers[:len(ref.agents)]):
-            assert bool(tr.active) == mine.drone.trackers[k].active, (t, k)
-            if tr.active:
+        mine.step(float(fx['action'][t]))
+        for k, active in enumerate(fx['active'][t]):
+            assert bool(active) == mine.drone.trackers[k].active, (t, k)
+            if active:
                 seen += 1
-                assert np.allclose(tr.mu_upds[-1][:, 0], mine.drone.trackers[k].mu_upds[-1][:, 0], rtol=0, atol=1e-6), (t, k)
-                assert np.allclose(tr.Sigma_upds[-1], mine.drone.trackers[k].Sigma_upds[-1], rtol=0, atol=1e-6), (t, k)
-        assert np.array_equal(ref.map_gt.grid_map, mine.map_gt.grid_map) and ref.tracked_agent == mine.tracked_agent
+                assert np.allclose(fx['mu'][t, k], mine.drone.trackers[k].mu_upds[-1][:, 0], rtol=0, atol=1e-6), (t, k)
+                assert np.allclose(fx['sigma'][t, k], mine.drone.trackers[k].Sigma_upds[-1], rtol=0, atol=1e-6), (t, k)
+        assert np.array_equal(fx['gt'][t], mine.map_gt.grid_map) and fx['tracked'][t] == mine.tracked_agent
     assert seen > 50
