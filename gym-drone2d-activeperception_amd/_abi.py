@@ -9,6 +9,7 @@ SM_WAIT_FOR_GOAL, SM_GOAL_REACHED, SM_PLANNING, SM_EXECUTING = 0, 1, 2, 3
 PLANNER_EXTERNAL, PLANNER_NOMOVE = 0, 1
 PLAN_NONE, PLAN_PRIMITIVE = 0, 1
 GAZE_NONE, GAZE_OXFORD = 0, 1
+GAZE_LOOKAHEAD, GAZE_LOOKGOAL = 2, 3   # yaw_planner.py:18-39 / :225-257 on the device
 NODE_F = 12
 
 AF = 6
@@ -79,6 +80,7 @@ def bind(lib, prefix='d2d_'):
         'closed_loop': (C.c_int, [P(Cfg), P(State), P(Plan), C.c_int32, C.c_int32, P(State), C.c_void_p]),
         'plan_reset': (C.c_int, [P(Cfg), P(Plan), C.c_void_p, C.c_int32, C.c_void_p]),
         'sincos_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+        'atan2_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         'launch_shape': (C.c_int, [P(Cfg), P(Plan), P(C.c_int32 * 4)]),
     }
     out = {}
@@ -92,6 +94,8 @@ def bind(lib, prefix='d2d_'):
     return out
 
 
-OPTIONAL = ('launch_shape',)
+# atan2_array: a test hook of the HIP library alone (include/d2d_hooks.h), outside the surface the oracle mirrors
+OPTIONAL = ('launch_shape', 'atan2_array')
+HIP_ONLY_ENTRY_POINTS = ('atan2_array',)
 ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_stages', 'rollout', 'reset',
                 'tan_array', 'gaze_stage', 'plan_stage', 'closed_loop', 'plan_reset', 'sincos_array', 'launch_shape')

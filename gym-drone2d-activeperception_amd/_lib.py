@@ -44,6 +44,7 @@ class HipBackend:
     """Thin call surface over the C ABI; launches go to torch's current HIP stream of `device`."""
     name = 'hip'
     supports_tiled_grids = True      # d2d_cfg.grid_tile = 16 (the CPU oracle keeps the reference's row-major grids)
+    supports_device_heading_gaze = True   # d2d_plan.gaze = LookAhead / LookGoal (the CPU oracle runs only Oxford's gaze stage)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -98,6 +99,9 @@ class HipBackend:
 
     def sincos_array(self, x, s, c):
         self._chk(self.fn['sincos_array'](x.data_ptr(), s.data_ptr(), c.data_ptr(), x.numel(), self._stream()))
+
+    def atan2_array(self, y, x, out):
+        self._chk(self.fn['atan2_array'](y.data_ptr(), x.data_ptr(), out.data_ptr(), y.numel(), self._stream()))
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

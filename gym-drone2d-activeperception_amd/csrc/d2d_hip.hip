@@ -45,6 +45,7 @@
 #define D2D_AS __attribute__((address_space(1)))
 #endif
 #include "../../include/d2d.h"
+#include "../../include/d2d_hooks.h"
 
 #define D2D_TAN_QUAL __device__ __forceinline__
 #define D2D_TAN_TBL_QUAL __device__ const
@@ -2241,6 +2242,11 @@ __global__ void k_tan(const double *in, double *out, long long n) {
 
 #include "d2d_plugins.h"
 
+__global__ void k_atan2(const double *y, const double *x, double *out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = d2d_atan2(y[i], x[i]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The closed loop as ONE persistent launch: every wave runs `nsteps` reference-style steps of its own env,
 //   [reset if the previous step ended the episode] -> Oxford.plan -> perceive -> Primitive.replan_check / plan -> act,
@@ -2703,9 +2709,16 @@ int plan_check(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p) {
   int rc = check(c, s);
   if (rc) return rc;
   if (!p) return fail(-1, "null plan");
+  if (p->gaze < D2D_GAZE_NONE || p->gaze > D2D_GAZE_LOOKGOAL) return fail(-1, "plan: unknown gaze policy");
   if (p->planner == D2D_PLAN_PRIMITIVE || p->gaze == D2D_GAZE_OXFORD) {
     if (!p->traj || !p->traj_hdr) return fail(-1, "plan: null trajectory buffers");
     if (!c->kf_enabled) return fail(-4, "device plugins need the Kalman trackers on the device (kf_enabled)");
+  }
+  if (p->gaze == D2D_GAZE_LOOKAHEAD || p->gaze == D2D_GAZE_LOOKGOAL) {
+    if (!s->action) return fail(-1, "plan: null action buffer");
+    if (!(p->yaw_rate_max > 0.0)) return fail(-1, "gaze: LookAhead / LookGoal need yaw_rate_max > 0");
+    if (p->gaze == D2D_GAZE_LOOKGOAL && (!p->traj || !p->traj_hdr || p->traj_cap <= 0))
+      return fail(-1, "gaze: LookGoal needs the trajectory buffers");
   }
   if (p->planner == D2D_PLAN_PRIMITIVE) {
     if (!p->u_space || !p->sample_t || !p->traj_t || !p->trk_radius || !p->trk_prev || !p->trk_lim || !p->nodes || !p->hash || !p->plan_stat)
@@ -2746,7 +2759,7 @@ int plan_check(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p) {
 
 // `init` != NULL: envs whose flags say "done" are first put back to the snapshot, plugin state included
 int gaze_launch(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, const d2d_state *init, bool skip_done, void *stream) {
-  if ((p->gaze != D2D_GAZE_OXFORD && !init) || c->B == 0) return 0;
+  if ((p->gaze == D2D_GAZE_NONE && !init) || c->B == 0) return 0;
   const size_t wb = p->gaze == D2D_GAZE_OXFORD ? (size_t)gaze_geom(*c, *p).wave_bytes : 0;
   int wpb = WAVES_PER_BLOCK;
   while (wpb > 1 && wb * wpb > LDS_SOFT) wpb >>= 1;
@@ -2873,7 +2886,7 @@ int d2d_closed_loop(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, int
     return fail(-1, "closed_loop: D2D_DONE_RESET needs the snapshot");
   if (c->B == 0 || nsteps == 0) return 0;
 #ifndef D2D_NO_PERSISTENT
-  if (c->planner_mode == D2D_PLANNER_EXTERNAL && p->launch_args && (p->planner == D2D_PLAN_PRIMITIVE || p->gaze == D2D_GAZE_OXFORD)) {
+  if (c->planner_mode == D2D_PLANNER_EXTERNAL && p->launch_args && (p->planner == D2D_PLAN_PRIMITIVE || p->gaze != D2D_GAZE_NONE)) {
     // one persistent launch: every wave loops over the steps of its own env.  Specialisation as for the step kernel;
     // as many envs (waves) per workgroup as the largest phase's LDS working set allows
     const int spec = !spec_path(*c) ? 0 : (c->N <= spec_ncap(1) ? 1 : (c->N <= spec_ncap(2) ? 2 : 3));
@@ -2971,6 +2984,16 @@ int d2d_tan_array(const double *in, double *out, int64_t n, void *stream) {
   const int bs = 256;
   hipLaunchKernelGGL(k_tan, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, in, out,
                      (long long)n);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
+  return 0;
+}
+
+int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, void *stream) {
+  if (n < 0 || (n > 0 && (!y || !x || !out))) return fail(-1, "atan2_array: bad arguments");
+  if (n == 0) return 0;
+  const int bs = 256;
+  hipLaunchKernelGGL(k_atan2, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, y, x, out, (long long)n);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
   return 0;

@@ -2,7 +2,7 @@
 // section 8 rows f2, f3).  Included by d2d_hip.hip inside its anonymous namespace.
 //
 //   k_plan   Primitive.replan_check + Primitive.plan (traj_planner.py:125-233) + the head waypoint step_pos consumes
-//   k_gaze   Oxford.plan (yaw_planner.py:81-127)
+//   k_gaze   Oxford.plan (yaw_planner.py:81-127), LookAhead.plan (:28-39), LookGoal.plan (:225-257)
 //
 // Mapping: ONE WAVEFRONT PER ENV, like the fused step: envs never talk to each other, every hand-off is lane ->
 // lane inside one wave (LDS, or the env's own global scratch behind wave_sync_global()).
@@ -29,6 +29,9 @@
 #define D2D_SINCOS_QUAL __device__ __forceinline__
 #define D2D_SINCOS_TBL_QUAL __device__ const
 #include "d2d_sincos.h"
+#define D2D_ATAN2_QUAL __device__ __forceinline__
+#define D2D_ATAN2_TBL_QUAL __device__ const
+#include "d2d_atan2.h"
 
 __device__ __forceinline__ double norm2(double x, double y) { return sqrt(__builtin_fma(y, y, x * x)); }
 
@@ -1303,6 +1306,62 @@ __host__ __device__ inline GazeGeom gaze_geom(const d2d_cfg &c, const d2d_plan &
   return g;
 }
 
+// LookAhead.plan (yaw_planner.py:28-39) or LookGoal.plan (:225-257) of env e by one wave, on the pose (x0, y0, yaw) the previous
+// step left: the heading in degrees, `math.degrees(math.atan2(..)) % 360` (d2d_atan2 = Python's math.atan2 bit for bit), and the
+// clipped yaw rate that turns towards it.  No LDS.  LookGoal looks at the first remaining waypoint whose cell of the drone's map is
+// UNEXPLORED (drone.map.get_grid, utils.py:545-548: 1 outside [0, map_size)), else at the last one; the waypoints go 64 at a time, a
+// ballot picks the first.  No trajectory: 0.
+__device__ __forceinline__ void heading_gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, int e, int lane,
+                                                 double x0, double y0, double yaw) {
+  double dy, dx;
+  if (p.gaze == D2D_GAZE_LOOKAHEAD) {
+    const double *dr = s.drone + (size_t)e * D2D_DF;
+    const double vx = dr[D2D_D_VX], vy = dr[D2D_D_VY];
+    if (vx == 0.0 && vy == 0.0) {
+      if (lane == 0) ((double *)s.action)[e] = 0.0;
+      return;
+    }
+    dy = -vy;
+    dx = vx;
+  } else {
+    const int *hdr = p.traj_hdr + (size_t)e * 2;
+    const int head = hdr[0], stored = hdr[1];
+    if (stored <= head) {
+      if (lane == 0) ((double *)s.action)[e] = 0.0;
+      return;
+    }
+    const double *__restrict__ traj = p.traj + (size_t)e * p.traj_cap * 4;
+    const unsigned char *__restrict__ dm = s.dmap + (size_t)e * grid_bytes(c);
+    const double inv_scale = 1.0 / c.scale;
+    int look = stored - 1;
+    for (int a0 = head; a0 < stored; a0 += WAVE) {
+      const int a = a0 + lane;
+      bool unexplored = false;
+      if (a < stored) {
+        const double2 w = ld2(traj + (size_t)a * 4);
+        if (!(w.x >= c.W_px || w.x < 0.0 || w.y >= c.H_px || w.y < 0.0)) {
+          const int ci = min(max(cell_fast(w.x, c.scale, inv_scale), 0), c.W - 1);
+          const int cj = min(max(cell_fast(w.y, c.scale, inv_scale), 0), c.H - 1);
+          unexplored = dm[grid_ix(c, ci, cj)] == D2D_UNEXPLORED;
+        }
+      }
+      const unsigned long long m = __ballot(unexplored);
+      if (m) {
+        look = a0 + __ffsll((long long)m) - 1;
+        break;
+      }
+    }
+    const double2 lw = ld2(traj + (size_t)look * 4);
+    dy = -(lw.y - y0);
+    dx = lw.x - x0;
+  }
+  const double heading = py_mod360(d2d_atan2(dy, dx) * 0x1.ca5dc1a63c1f8p+5);  // math.degrees: r * (180 / pi)
+  const double m = p.yaw_rate_max, delta = heading - yaw;
+  // max(min(delta / dt, m), -m) with Python's min / max (a NaN passes through, as on the host)
+  const double q = delta / c.dt, lo = (m < q) ? m : q, rate = (-m > lo) ? -m : lo;
+  if (lane == 0) ((double *)s.action)[e] = (fabs(delta) < 180.0 ? rate : -rate) / m;
+}
+
 // Reset-if-done + Oxford.plan of env e by one wave; `base`: gaze_geom().wave_bytes bytes of LDS.
 // `auto_reset`: an env whose previous step ended its episode (flags[D2D_F_DONE]) first goes back to the snapshot
 // `init` with fresh plugin state -- the next episode of the reference's sweeps (main.py:26-57).
@@ -1341,7 +1400,10 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
       stored = hdr[1];
     }
   }
-  if (!oxford) return;
+  if (!oxford) {
+    if (p.gaze == D2D_GAZE_LOOKAHEAD || p.gaze == D2D_GAZE_LOOKGOAL) heading_gaze_env(c, s, p, e, lane, x0, y0, yaw);
+    return;
+  }
 #ifdef D2D_CHAIN_PROF
   unsigned long long gz_t = __builtin_amdgcn_s_memtime();
 #endif

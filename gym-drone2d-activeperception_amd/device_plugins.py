@@ -230,7 +230,7 @@ class PluginState:
         sc, tb = tables if tables is not None else build_tables(params, cfg, need_acos=(gaze == 'Oxford'))
         self.scalars, self.tables_np = sc, tb
         self.planner = A.PLAN_PRIMITIVE if planner == 'Primitive' else A.PLAN_NONE
-        self.gaze = A.GAZE_OXFORD if gaze == 'Oxford' else A.GAZE_NONE
+        self.gaze = {'Oxford': A.GAZE_OXFORD, 'LookAhead': A.GAZE_LOOKAHEAD, 'LookGoal': A.GAZE_LOOKGOAL}.get(gaze, A.GAZE_NONE)
         B, N = cfg.B, cfg.N
         dev = self.device
         self.tables = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in tb.items()}

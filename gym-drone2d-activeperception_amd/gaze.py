@@ -9,9 +9,11 @@ experiment.py:33-34,69); the classes here work that way and as ordinary instance
 action buffer on the device, `env.step` recognises the token and uploads nothing; `float(action)` reads it back for
 callers that want the number.  `NoControl` and `Rotating` are the reference's constants; `LookAhead` (the method
 main.py:10 and script/train.py:18 select) and `LookGoal` are a dozen scalar operations on what the step already
-mirrors to the host (velocity, yaw; the stored trajectory and the drone's map), so they run here on the host with
-the same libm calls as the reference (`math.atan2`, `math.degrees`, float `%`); so does `Owl` (36 direction scores
-and 20 candidate yaw rates per decision, one decision every 0.8 s).  Any other policy (the reference's `Oxford` as a
+mirrors to the host (velocity, yaw; the stored trajectory and the drone's map), so the classes here run them on the
+host with the same libm calls as the reference (`math.atan2`, `math.degrees`, float `%`) -- the facade's path and the
+oracle's; batches run the same two policies as device gaze stages (`VecDrone2DEnv(..., device_plugins=True,
+gaze='LookAhead' / 'LookGoal')`, `runner.ExperimentBatch`; csrc/d2d_atan2.h returns math.atan2's bits).  `Owl` (36
+direction scores and 20 candidate yaw rates per decision, one decision every 0.8 s) is a host policy only.  Any other policy (the reference's `Oxford` as a
 host object, a user's class) is a host plugin too: it reads the env through the `info` proxies; names this registry
 does not know resolve through the reference's `yaw_planner` module when that is importable.
 """

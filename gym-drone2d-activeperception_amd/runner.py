@@ -63,31 +63,40 @@ class Experiment:
 class ExperimentBatch:
     """The reference's sweep of episodes (`main.py:26-57`: the same cfg over many map ids, one Experiment and one
     CSV row each) as ONE device batch: env i is the world of `map_id + i`, the gaze policy and the planner run on
-    the device (Oxford / Primitive), every env plays exactly one episode (`D2D_DONE_FREEZE`) and `rows()` returns
-    the reference's CSV rows.  Everything an episode needs stays on the GPU; the host only reads the rows.
+    the device (Oxford / LookAhead / LookGoal / Primitive), every env plays exactly one episode (`D2D_DONE_FREEZE`)
+    and `rows()` returns the reference's CSV rows.  Everything an episode needs stays on the GPU; the host only reads
+    the rows.
 
-    `LookAhead` (main.py:10's default method) is the one host policy a batch runs: it needs the drone's velocity and yaw
-    only, so every step pulls those three numbers per env, evaluates yaw_planner.py:28-39 with the host's libm (the
-    reference's `math.atan2`; there is no bit-exact device atan2 here) and uploads the actions -- one launch per step
-    instead of one per episode."""
+    `LookAhead` (main.py:10's default method) and `LookGoal` run as the device gaze stage (yaw_planner.py:28-39,
+    :225-257 with a bit-exact restatement of `math.atan2`), one `closed_loop` call per chunk like Oxford.  On a backend
+    without that stage (`supports_device_heading_gaze`, e.g. the CPU oracle) LookAhead runs from the host instead: every
+    step pulls the drone's velocity and yaw, evaluates the policy with the host's libm and uploads the actions -- one
+    launch per step instead of one per episode; LookGoal is refused there.  `device_gaze=False` takes that host path for
+    LookAhead on any backend (A/B measurements)."""
 
-    def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0):
+    def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_gaze=True):
         from .vec_env import VecDrone2DEnv, build_worlds
+        from ._lib import HipBackend
         p = with_defaults(params)
-        if p.gaze_method not in ('Oxford', 'Rotating', 'NoControl', 'LookAhead') or p.planner not in ('Primitive', 'NoMove'):
-            raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / Rotating / NoControl (and '
-                                      'LookAhead from the host), planner Primitive / NoMove (use Experiment, one episode at a '
-                                      'time, for other host plugin classes)')
+        if p.gaze_method not in ('Oxford', 'Rotating', 'NoControl', 'LookAhead', 'LookGoal') or p.planner not in ('Primitive', 'NoMove'):
+            raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / LookAhead / LookGoal / Rotating '
+                                      '/ NoControl, planner Primitive / NoMove (use Experiment, one episode at a time, for other '
+                                      'host plugin classes)')
+        device_heading = device_gaze and getattr(backend if backend is not None else HipBackend, 'supports_device_heading_gaze', False)
+        if p.gaze_method == 'LookGoal' and not device_heading:
+            raise NotImplementedError('ExperimentBatch: LookGoal needs a backend with the device LookAhead / LookGoal stage')
+        self._host_lookahead = p.gaze_method == 'LookAhead' and not device_heading
         if p.gaze_method == 'NoControl':
             p.drone_view_range = 360                                   # experiment.py:28-29
         self.params = p
         worlds = build_worlds(p, num_envs, workers=workers)
         self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
-                                 device_plugins=True, gaze='external' if p.gaze_method == 'LookAhead' else p.gaze_method)
+                                 device_plugins=True, gaze='external' if self._host_lookahead else p.gaze_method)
         self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
 
     def _lookahead_actions(self):
-        """yaw_planner.LookAhead.plan for every env (gaze.LookAhead, vectorised over the batch on the host)."""
+        """yaw_planner.LookAhead.plan for every env (gaze.LookAhead, vectorised over the batch on the host): the path of a
+        backend without the device stage."""
         from .gaze import _yaw_rate_towards
         import math
         p = self.params
@@ -100,7 +109,7 @@ class ExperimentBatch:
 
     def run(self, chunk=None):
         n = self.max_steps
-        if self.params.gaze_method == 'LookAhead':
+        if self._host_lookahead:
             for t in range(n):
                 self.env._set_action(self._lookahead_actions())
                 self.env.closed_loop(1, freeze_done=True)

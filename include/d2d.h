@@ -54,6 +54,10 @@ extern "C" {
 /* d2d_plan.gaze: which gaze policy d2d_gaze_stage runs before the step */
 #define D2D_GAZE_NONE 0   /* action stays as the caller wrote it                                      */
 #define D2D_GAZE_OXFORD 1 /* yaw_planner.py:41-127 on device                                          */
+#define D2D_GAZE_LOOKAHEAD 2 /* yaw_planner.py:18-39 on device: turn towards the velocity, atan2(-vy, vx) (the host loop of
+                                main.py:10's default policy it replaces); needs plan.yaw_rate_max > 0                    */
+#define D2D_GAZE_LOOKGOAL 3  /* yaw_planner.py:225-257 on device: turn towards the first remaining waypoint in an UNEXPLORED
+                                cell of the drone's map, else the last one; needs traj / traj_hdr and yaw_rate_max > 0 */
 
 /* agent field planes of d2d_state.agents: [B][D2D_AF][N] */
 #define D2D_AF 6
@@ -355,7 +359,8 @@ int d2d_tan_array(const double *in, double *out, int64_t n, void *stream);
 
 /* policy.plan(info) of the gaze plugin for every env (experiment.py:69), run BEFORE the step on the state the
  * previous step left: writes st->action.  D2D_GAZE_OXFORD: yaw_planner.py:81-127 (view map of the current pose,
- * time-since-observed map, swept-trajectory reward, 6 yaw-rate candidates).  D2D_GAZE_NONE: no-op. */
+ * time-since-observed map, swept-trajectory reward, 6 yaw-rate candidates).  D2D_GAZE_LOOKAHEAD / D2D_GAZE_LOOKGOAL:
+ * yaw_planner.py:28-39 / :225-257 (a heading by Python's math.atan2, one clipped yaw rate).  D2D_GAZE_NONE: no-op. */
 int d2d_gaze_stage(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan, void *stream);
 
 /* planner.replan_check(drone) + planner.plan(drone, dt) (envs/drone_v2.py:194-197) + the head waypoint

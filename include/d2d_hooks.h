@@ -1,0 +1,24 @@
+/*
+ * d2d_hooks.h — test hooks of the HIP library (libd2d_hip.so) alone.
+ *
+ * include/d2d.h is the surface both implementations export (the CPU oracle as d2d_oracle_*); the entry points
+ * here exist only where there is a device restatement to check, so they stay out of that shared surface.
+ */
+#ifndef D2D_HOOKS_H
+#define D2D_HOOKS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Device restatement of Python's math.atan2 (CPython's special cases over the host libm atan2) that the LookAhead and
+ * LookGoal gaze stages call (yaw_planner.py:33, :251): out[i] = atan2(y[i], x[i]), bit-for-bit glibc 2.35 x86-64
+ * FMA variant.  Returns 0, or a negative error like every entry point. */
+int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* D2D_HOOKS_H */
