@@ -123,13 +123,18 @@ def test_closed_loop_matches_oracle(pkg, hip, oracle, case):
         oracle_threads(1)
 
 
-@pytest.mark.parametrize('kw', [dict(agent_number=14, agent_radius=12, agent_max_speed=40, map_id=30),
-                                dict(agent_number=14, agent_radius=12, agent_max_speed=40, map_id=30, drone_view_range=100)],
+@pytest.mark.parametrize('kw,path', [(dict(agent_number=14, agent_radius=12, agent_max_speed=40, map_id=30), 'k_closed<1>'),
+                                     (dict(agent_number=14, agent_radius=12, agent_max_speed=40, map_id=30, drone_view_range=100),
+                                      'per_stage_primitive')],
                          ids=['persistent', 'per_stage'])
-def test_freeze_mode_matches_oracle(pkg, hip, oracle, kw):
+def test_freeze_mode_matches_oracle(pkg, hip, oracle, kw, path):
     """D2D_DONE_FREEZE: one episode per env, finished envs stay exactly as they ended -- on the persistent kernel
-    (default geometry) and on the launch-per-stage path (any other geometry)."""
+    (default geometry) and on the launch-per-stage path (launch_args = NULL; another geometry as well)."""
+    from closed_loop_cases import closed_loop_path
     dev, ref = _pair(pkg, hip, oracle, 12, **kw)
+    if path == 'per_stage_primitive':
+        dev._plan.launch_args = None
+    assert closed_loop_path(dev.cfg, dev._plan) == path
     oracle.lib.d2d_oracle_set_threads(8)
     try:
         for _ in range(6):
