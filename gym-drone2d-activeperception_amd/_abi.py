@@ -10,6 +10,11 @@ PLANNER_EXTERNAL, PLANNER_NOMOVE = 0, 1
 PLAN_NONE, PLAN_PRIMITIVE = 0, 1
 GAZE_NONE, GAZE_OXFORD = 0, 1
 GAZE_LOOKAHEAD, GAZE_LOOKGOAL = 2, 3   # yaw_planner.py:18-39 / :225-257 on the device
+GAZE_OWL = 5                           # yaw_planner.py:151-222 on the device (4 is unassigned)
+# d2d_plan.owl_tab / owl_state layouts (include/d2d.h D2D_OWL_*)
+OWL_NRATE, OWL_NDIR = 20, 36
+OWL_T_RATE, OWL_T_RATE08, OWL_T_TURN, OWL_T_ACT, OWL_T_DIR, OWL_T_FOV, OWL_T_DEPTH, OWL_T_HOLD, OWL_TAB_LEN = 0, 20, 40, 60, 80, 152, 153, 154, 160
+OWL_STATE_F, OWL_S_RATE, OWL_S_LEFT = 40, 36, 37
 NODE_F = 12
 
 AF = 6
@@ -50,8 +55,8 @@ class State(C.Structure):
 PLAN_INT_FIELDS = ('planner', 'gaze', 'nu', 'n_sample', 'n_ts', 'max_itr', 'traj_cap', 'node_cap', 'hash_cap', 'n_yaw',
                    'pw_nleaf', 'pw_nprog', 'tobs_len', 'pw_ntree')
 PLAN_F64_FIELDS = ('horizon', 'vmax', 'safe_dist', 'goal_tol', 'agent_radius', 'half_fov', 'yaw_rate_max', 'vmax_sq', 'goal_sq')
-PLAN_TABLES = ('u_space', 'sample_t', 'traj_t', 'yaw_space', 'tobs_tab', 'pw_leaf', 'pw_prog', 'pw_tree', 'pw_rowleaf', 'trk_radius0')
-PLAN_STATE = ('traj', 'traj_hdr', 'traj_box', 'trk_radius', 'trk_prev', 'trk_lim', 'seen_step', 'nodes', 'hash', 'launch_args', 'plan_stat')
+PLAN_TABLES = ('u_space', 'sample_t', 'traj_t', 'yaw_space', 'tobs_tab', 'pw_leaf', 'pw_prog', 'pw_tree', 'pw_rowleaf', 'trk_radius0', 'owl_tab')
+PLAN_STATE = ('traj', 'traj_hdr', 'traj_box', 'trk_radius', 'trk_prev', 'trk_lim', 'seen_step', 'nodes', 'hash', 'launch_args', 'plan_stat', 'owl_state')
 LAUNCH_ARGS_BYTES = 2048
 
 
@@ -81,6 +86,7 @@ def bind(lib, prefix='d2d_'):
         'plan_reset': (C.c_int, [P(Cfg), P(Plan), C.c_void_p, C.c_int32, C.c_void_p]),
         'sincos_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         'atan2_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+        'pow2_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         'launch_shape': (C.c_int, [P(Cfg), P(Plan), P(C.c_int32 * 4)]),
     }
     out = {}
@@ -94,8 +100,8 @@ def bind(lib, prefix='d2d_'):
     return out
 
 
-# atan2_array: a test hook of the HIP library alone (include/d2d_hooks.h), outside the surface the oracle mirrors
-OPTIONAL = ('launch_shape', 'atan2_array')
-HIP_ONLY_ENTRY_POINTS = ('atan2_array',)
+# atan2_array, pow2_array: test hooks of the HIP library alone (include/d2d_hooks.h), outside the surface the oracle mirrors
+OPTIONAL = ('launch_shape', 'atan2_array', 'pow2_array')
+HIP_ONLY_ENTRY_POINTS = ('atan2_array', 'pow2_array')
 ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_stages', 'rollout', 'reset',
                 'tan_array', 'gaze_stage', 'plan_stage', 'closed_loop', 'plan_reset', 'sincos_array', 'launch_shape')

@@ -45,6 +45,7 @@ class HipBackend:
     name = 'hip'
     supports_tiled_grids = True      # d2d_cfg.grid_tile = 16 (the CPU oracle keeps the reference's row-major grids)
     supports_device_heading_gaze = True   # d2d_plan.gaze = LookAhead / LookGoal (the CPU oracle runs only Oxford's gaze stage)
+    supports_device_owl_gaze = True       # d2d_plan.gaze = Owl
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -102,6 +103,9 @@ class HipBackend:
 
     def atan2_array(self, y, x, out):
         self._chk(self.fn['atan2_array'](y.data_ptr(), x.data_ptr(), out.data_ptr(), y.numel(), self._stream()))
+
+    def pow2_array(self, x, out):
+        self._chk(self.fn['pow2_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -2454,7 +2454,7 @@ __device__ D2D_PH_ATTR int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_
 #ifdef D2D_CHAIN_PROF
   const unsigned long long pp0 = __builtin_amdgcn_s_memtime();
 #endif
-  gaze_env(c, a->s, a->p, a->init, a->on_done == D2D_DONE_RESET, e, lane, base, known_done);
+  gaze_env<true>(c, a->s, a->p, a->init, a->on_done == D2D_DONE_RESET, e, lane, base, known_done);
   wave_sync_global();
 #ifdef D2D_CHAIN_PROF
   D2D_PHASE_ADD(0, pp0);
@@ -2709,7 +2709,9 @@ int plan_check(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p) {
   int rc = check(c, s);
   if (rc) return rc;
   if (!p) return fail(-1, "null plan");
-  if (p->gaze < D2D_GAZE_NONE || p->gaze > D2D_GAZE_LOOKGOAL) return fail(-1, "plan: unknown gaze policy");
+  if (p->gaze != D2D_GAZE_NONE && p->gaze != D2D_GAZE_OXFORD && p->gaze != D2D_GAZE_LOOKAHEAD && p->gaze != D2D_GAZE_LOOKGOAL &&
+      p->gaze != D2D_GAZE_OWL)
+    return fail(-1, "plan: unknown gaze policy");
   if (p->planner == D2D_PLAN_PRIMITIVE || p->gaze == D2D_GAZE_OXFORD) {
     if (!p->traj || !p->traj_hdr) return fail(-1, "plan: null trajectory buffers");
     if (!c->kf_enabled) return fail(-4, "device plugins need the Kalman trackers on the device (kf_enabled)");
@@ -2719,6 +2721,12 @@ int plan_check(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p) {
     if (!(p->yaw_rate_max > 0.0)) return fail(-1, "gaze: LookAhead / LookGoal need yaw_rate_max > 0");
     if (p->gaze == D2D_GAZE_LOOKGOAL && (!p->traj || !p->traj_hdr || p->traj_cap <= 0))
       return fail(-1, "gaze: LookGoal needs the trajectory buffers");
+  }
+  if (p->gaze == D2D_GAZE_OWL) {
+    if (!s->action) return fail(-1, "plan: null action buffer");
+    if (!(p->yaw_rate_max > 0.0)) return fail(-1, "gaze: Owl needs yaw_rate_max > 0");
+    if (!p->owl_tab || !p->owl_state) return fail(-1, "gaze: Owl needs owl_tab and owl_state");
+    if (!c->kf_enabled || !s->kf) return fail(-1, "gaze: Owl needs the Kalman trackers on the device (kf)");
   }
   if (p->planner == D2D_PLAN_PRIMITIVE) {
     if (!p->u_space || !p->sample_t || !p->traj_t || !p->trk_radius || !p->trk_prev || !p->trk_lim || !p->nodes || !p->hash || !p->plan_stat)
@@ -2765,8 +2773,12 @@ int gaze_launch(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, const d
   while (wpb > 1 && wb * wpb > LDS_SOFT) wpb >>= 1;
   const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
   const size_t lds = wb * wpb;
-  lds_optin(k_gaze, lds);
-  hipLaunchKernelGGL(k_gaze, grid, block, lds, (hipStream_t)stream, *c, *s, *p, init ? *init : *s, init ? 1 : (skip_done ? 2 : 0));
+  if (p->gaze == D2D_GAZE_OWL) {
+    hipLaunchKernelGGL(k_gaze_owl, grid, block, 0, (hipStream_t)stream, *c, *s, *p, init ? *init : *s, init ? 1 : (skip_done ? 2 : 0));
+  } else {
+    lds_optin(k_gaze, lds);
+    hipLaunchKernelGGL(k_gaze, grid, block, lds, (hipStream_t)stream, *c, *s, *p, init ? *init : *s, init ? 1 : (skip_done ? 2 : 0));
+  }
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
   return 0;
@@ -2994,6 +3006,16 @@ int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, vo
   if (n == 0) return 0;
   const int bs = 256;
   hipLaunchKernelGGL(k_atan2, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, y, x, out, (long long)n);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
+  return 0;
+}
+
+int d2d_pow2_array(const double *x, double *out, int64_t n, void *stream) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(-1, "pow2_array: bad arguments");
+  if (n == 0) return 0;
+  const int bs = 256;
+  hipLaunchKernelGGL(k_pow2, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, x, out, (long long)n);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
   return 0;

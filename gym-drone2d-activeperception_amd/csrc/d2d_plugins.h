@@ -2,7 +2,7 @@
 // section 8 rows f2, f3).  Included by d2d_hip.hip inside its anonymous namespace.
 //
 //   k_plan   Primitive.replan_check + Primitive.plan (traj_planner.py:125-233) + the head waypoint step_pos consumes
-//   k_gaze   Oxford.plan (yaw_planner.py:81-127), LookAhead.plan (:28-39), LookGoal.plan (:225-257)
+//   k_gaze   Oxford.plan (yaw_planner.py:81-127), LookAhead.plan (:28-39), LookGoal.plan (:225-257), Owl.plan (:187-222)
 //
 // Mapping: ONE WAVEFRONT PER ENV, like the fused step: envs never talk to each other, every hand-off is lane ->
 // lane inside one wave (LDS, or the env's own global scratch behind wave_sync_global()).
@@ -32,6 +32,9 @@
 #define D2D_ATAN2_QUAL __device__ __forceinline__
 #define D2D_ATAN2_TBL_QUAL __device__ const
 #include "d2d_atan2.h"
+#define D2D_POW2_QUAL __device__ __forceinline__
+#define D2D_POW2_TBL_QUAL __device__ const
+#include "d2d_pow2.h"
 
 __device__ __forceinline__ double norm2(double x, double y) { return sqrt(__builtin_fma(y, y, x * x)); }
 
@@ -1236,6 +1239,7 @@ __device__ __forceinline__ void plan_reset_env(const d2d_cfg &c, const d2d_plan 
   }
   if (p.seen_step)
     for (size_t i = lane; i < WH; i += WAVE) p.seen_step[e * WH + i] = 0;
+  if (p.owl_state && lane < D2D_OWL_STATE_F) p.owl_state[e * D2D_OWL_STATE_F + lane] = 0.0;
 }
 
 
@@ -1362,6 +1366,151 @@ __device__ __forceinline__ void heading_gaze_env(const d2d_cfg &c, const d2d_sta
   if (lane == 0) ((double *)s.action)[e] = (fabs(delta) < 180.0 ? rate : -rate) / m;
 }
 
+// ---- Owl (yaw_planner.py:151-222) ----
+// angle_between (:144-149) of two angles already reduced `% 360`; np.minimum hands a NaN on
+__device__ __forceinline__ double owl_apart(double am, double bm) {
+  const double d = fabs(am - bm), f = 360.0 - d;
+  return (d < f) ? d : f;
+}
+
+// Owl.G (:169-173): 0 inside the field of view, else the product of the angles (radians) to its two edges.  `hp`, `hn`:
+// (fov / 2) % 360 and (-fov / 2) % 360.  A NaN direction fails the `<=` and comes back as NaN, as on the host.
+__device__ __forceinline__ double owl_unseen(double theta, double half, double hp, double hn) {
+  const double deg2rad = 0x1.1df46a2529d39p-6;  // math.radians
+  const double m = py_mod360(theta);
+  if (owl_apart(m, 0.0) <= half) return 0.0;
+  return (owl_apart(m, hp) * deg2rad) * (owl_apart(m, hn) * deg2rad);
+}
+
+// Owl.plan of env e by one wave, on the pose (x0, y0, yaw) the previous step left.  No LDS.  A decision refreshes the 36
+// ten-degree direction scores (update_U, lanes 0..35), looks the scores of the goal and flight directions up, costs the 20
+// candidate yaw rates (lanes 0..19) and picks the cheapest with np.argmin's rules; the pick is then repeated for
+// owl_tab[D2D_OWL_T_HOLD] further calls (`self.u`, :189-192, :220-222).  Every constant the reference derives with numpy / Python
+// arithmetic comes from owl_tab (include/d2d.h); every operation below is one of the reference's, in its order: numpy's
+// two-element dot and norm are fma(b1, b2, a1 * a2), `f[i, :].dot(lamb)` is a chain of five FMAs from 0, `** 2` is libm's
+// pow(x, 2.0) (d2d_pow2.h).  A drone at rest makes d_v NaN, hence every cost NaN, hence candidate 0: nothing here special-cases
+// it.  The per-stage launch runs this stage in a kernel of its own (k_gaze_owl), so that k_gaze keeps its allocation.
+#ifndef D2D_OWL_ATTR
+#define D2D_OWL_ATTR __forceinline__
+#endif
+__device__ D2D_OWL_ATTR void owl_gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, int e, int lane,
+                                                       double x0, double y0, double yaw) {
+  const double D2D_AS *__restrict__ tab = p.owl_tab;
+  double D2D_AS *st = p.owl_state + (size_t)e * D2D_OWL_STATE_F;
+  double *act = (double *)s.action;
+  const double left = st[D2D_OWL_S_LEFT];
+  if (left > 0.0) {  // `if len(self.u) != 0: return self.u.pop() / top`
+    if (lane == 0) {
+      st[D2D_OWL_S_LEFT] = left - 1.0;
+      act[e] = st[D2D_OWL_S_RATE] / p.yaw_rate_max;
+    }
+    return;
+  }
+  const double rad2deg = 0x1.ca5dc1a63c1f8p+5;  // math.degrees: r * (180 / pi)
+  const double *dr = s.drone + (size_t)e * D2D_DF;
+  const double vx = dr[D2D_D_VX], vy = dr[D2D_D_VY];
+  const double tx = s.target[(size_t)e * 2], ty = s.target[(size_t)e * 2 + 1];
+  const double half = tab[D2D_OWL_T_FOV] * 0.5, depth = tab[D2D_OWL_T_DEPTH];
+  const double hp = py_mod360(half), hn = py_mod360(-half);
+  const int N = c.N;
+
+  // update_U (:175-181): lane k < 36 owns direction 10 k degrees
+  double sc_l = 0.0;
+  if (lane < D2D_OWL_NDIR) {
+    const double cs = tab[D2D_OWL_T_DIR + 2 * lane], sn = tab[D2D_OWL_T_DIR + 2 * lane + 1];
+    const double mx = vx * 0.8, my = vy * 0.8;
+    double g = -__builtin_fma(my, sn, mx * cs) / depth;
+    g += (owl_apart(10.0 * lane, py_mod360(-yaw)) < half) ? 0.4 : -0.05;
+    const double v = st[lane] + g;
+    // max(min(v, 1), 0) with Python's min / max (a NaN passes through, as on the host)
+    const double lo = (1.0 < v) ? 1.0 : v;
+    sc_l = (0.0 > lo) ? 0.0 : lo;
+    st[lane] = sc_l;
+  }
+
+  // d_g (lane 20) and d_v (every other lane; lane 21's is used), :200-201
+  const double vn = norm2(vx, vy);
+  const double ang = d2d_atan2(lane == 20 ? ty - y0 : vy / vn, lane == 20 ? tx - x0 : vx / vn) * rad2deg;
+  const double d_g = shfl_f64(ang, 20), d_v = shfl_f64(ang, 21);
+
+  // U(theta) (:183-185) for the candidates' headings (lanes 0..19), d_g (lane 20) and d_v (lane 21): the first nearest of the
+  // 36 directions; a NaN theta makes every distance NaN and np.argmin answers 0
+  const double r08 = tab[D2D_OWL_T_RATE08 + min(lane, D2D_OWL_NRATE - 1)];
+  const double h = -(yaw + r08);
+  const double th = py_mod360(lane < D2D_OWL_NRATE ? h : (lane == 20 ? d_g : d_v));
+  int near = 0;
+  double near_d = owl_apart(0.0, th);
+  for (int k = 1; k < D2D_OWL_NDIR; ++k) {
+    const double a = owl_apart(10.0 * k, th);
+    if (a < near_d) {
+      near = k;
+      near_d = a;
+    }
+  }
+  const double u_l = shfl_f64(sc_l, near);
+  const double goal_unknown = 1.0 - shfl_f64(u_l, 20), flight_unknown = 1.0 - shfl_f64(u_l, 21);
+
+  // f[i, 0], f[i, 1] (:208-209)
+  const double t0 = owl_unseen(h - d_g, half, hp, hn) * goal_unknown;
+  const double speed2 = d2d_pow2(norm2(vx / 10.0, vy / 10.0));
+  const double t1 = (speed2 * owl_unseen(h - d_v, half, hp, hn)) * flight_unknown;
+
+  // f[i, 2] (:211-212): d_o lists the ACTIVE trackers in index order; `zip(d_o, trackers)` weights the j-th of them with the
+  // state of tracker j, whichever tracker that is.  64 list entries at a time: lane l finds the l-th active tracker of the
+  // chunk, its direction and the weight; the candidates then add the entries in list order.
+  int nact = 0;
+  for (int b0 = 0; b0 < N; b0 += WAVE) {
+    const int t = b0 + lane;
+    nact += __popcll(__ballot(t < N && s.active[(size_t)e * N + t] != 0));
+  }
+  const double *kf = s.kf + (size_t)e * N * D2D_KF;
+  double t2 = 0.0;
+  for (int j0 = 0; j0 < nact; j0 += WAVE) {
+    const int j = j0 + lane;
+    int mine = 0, seen = 0;
+    for (int b0 = 0; b0 < N; b0 += WAVE) {
+      const int t = b0 + lane;
+      unsigned long long m = __ballot(t < N && s.active[(size_t)e * N + t] != 0);
+      while (m) {
+        if (seen == j) mine = b0 + __ffsll((long long)m) - 1;
+        ++seen;
+        m &= m - 1;
+      }
+    }
+    double d_o = 0.0, pull = 0.0;
+    if (j < nact) {
+      const double *ma = kf + (size_t)mine * D2D_KF, *mj = kf + (size_t)j * D2D_KF;
+      d_o = d2d_atan2(ma[1] - y0, ma[0] - x0) * rad2deg;
+      pull = norm2(mj[2], mj[3]) / norm2(mj[0] - x0, mj[1] - y0);  // beta = 1
+    }
+    const int cnt = min(nact - j0, WAVE);
+    for (int q = 0; q < cnt; ++q) t2 += shfl_f64(pull, q) * owl_unseen(h - shfl_f64(d_o, q), half, hp, hn);
+  }
+
+  // f[i, :].dot(lamb) (:217), lamb = [0.2, 0.9, 1, 0.1, 0]
+  double cost = __builtin_fma(t0, 0.2, 0.0);
+  cost = __builtin_fma(t1, 0.9, cost);
+  cost = __builtin_fma(t2, 1.0, cost);
+  cost = __builtin_fma(u_l, 0.1, cost);
+  cost = __builtin_fma(tab[D2D_OWL_T_TURN + min(lane, D2D_OWL_NRATE - 1)], 0.0, cost);
+
+  // np.argmin (:218): the first minimum; the first NaN wins outright
+  int best = 0;
+  double best_c = shfl_f64(cost, 0);
+  for (int a = 1; a < D2D_OWL_NRATE; ++a) {
+    const double v = shfl_f64(cost, a);
+    if (best_c == best_c && (v < best_c || v != v)) {
+      best = a;
+      best_c = v;
+    }
+  }
+  if (lane == 0) {
+    st[D2D_OWL_S_RATE] = tab[D2D_OWL_T_RATE + best];
+    st[D2D_OWL_S_LEFT] = tab[D2D_OWL_T_HOLD];
+    act[e] = tab[D2D_OWL_T_ACT + best];
+  }
+}
+
 // Reset-if-done + Oxford.plan of env e by one wave; `base`: gaze_geom().wave_bytes bytes of LDS.
 // `auto_reset`: an env whose previous step ended its episode (flags[D2D_F_DONE]) first goes back to the snapshot
 // `init` with fresh plugin state -- the next episode of the reference's sweeps (main.py:26-57).
@@ -1369,6 +1518,8 @@ __device__ __forceinline__ void heading_gaze_env(const d2d_cfg &c, const d2d_sta
 // than arithmetic, so loads are batched: one sin / cos pass for all seven view directions, every lane's seen-map
 // cells fetched before the first is used, the pairwise plan staged in LDS.
 // `known_done`: the env's episode flag where the caller holds it (the persistent loop), -1: read here.
+// OWL: whether the caller's kernel carries the Owl stage (k_gaze does not: the stage has k_gaze_owl).
+template <bool OWL>
 __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, const d2d_state &init,
                                          int auto_reset, int e, int lane, char *base, int known_done = -1) {
   // ---- one batch of loads: everything the stage needs that does not hang on another load (the episode flag, the pose, the step
@@ -1402,6 +1553,9 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
   }
   if (!oxford) {
     if (p.gaze == D2D_GAZE_LOOKAHEAD || p.gaze == D2D_GAZE_LOOKGOAL) heading_gaze_env(c, s, p, e, lane, x0, y0, yaw);
+    if constexpr (OWL) {
+      if (p.gaze == D2D_GAZE_OWL) owl_gaze_env(c, s, p, e, lane, x0, y0, yaw);
+    }
     return;
   }
 #ifdef D2D_CHAIN_PROF
@@ -2070,7 +2224,22 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_gaze(d2d_cfg c, d2d_s
   const int e = blockIdx.x * (int)(blockDim.x / WAVE) + wv;
   if (e >= c.B) return;
   if (mode == 2 && s.flags[(size_t)e * 4 + D2D_F_DONE] != 0) return;
-  gaze_env(c, s, p, init, mode == 1, e, lane, d2d_lds + (size_t)wv * gaze_geom(c, p).wave_bytes);
+  gaze_env<false>(c, s, p, init, mode == 1, e, lane, d2d_lds + (size_t)wv * gaze_geom(c, p).wave_bytes);
+}
+
+// k_gaze for D2D_GAZE_OWL (no LDS)
+__global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_gaze_owl(d2d_cfg c, d2d_state s, d2d_plan p, d2d_state init, int mode) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int e = blockIdx.x * (int)(blockDim.x / WAVE) + wv;
+  if (e >= c.B || p.gaze != D2D_GAZE_OWL) return;
+  if (mode == 2 && s.flags[(size_t)e * 4 + D2D_F_DONE] != 0) return;
+  gaze_env<true>(c, s, p, init, mode == 1, e, lane, d2d_lds);
+}
+
+__global__ void k_pow2(const double *x, double *out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = d2d_pow2(x[i]);
 }
 
 __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_plan_reset(d2d_cfg c, d2d_plan p, const unsigned char *mask,

@@ -1,11 +1,11 @@
 """Host side of the device planner / gaze plugins (include/d2d.h `d2d_plan`).
 
-The device replays the reference's `Primitive` planner (traj_planner.py:78-233) and `Oxford` gaze policy
-(yaw_planner.py:41-127) operation for operation.  Every constant those classes derive with numpy / Python
+The device replays the reference's `Primitive` planner (traj_planner.py:78-233) and its `Oxford`, `LookAhead`, `LookGoal`
+and `Owl` gaze policies (yaw_planner.py:18-257) operation for operation.  Every constant those classes derive with numpy / Python
 float arithmetic is evaluated HERE, with the very expressions the reference uses, and handed over as small
 tables: the device never has to guess how `np.arange`, `t ** 2` or `np.arccos` round.
 
-`PluginState` owns the tables, the per-env plugin state (trajectory, tracker radii, Oxford's seen map) and
+`PluginState` owns the tables, the per-env plugin state (trajectory, tracker radii, Oxford's seen map, Owl's scores) and
 the search scratch as torch tensors on the batch's device, and builds the ctypes `d2d_plan` over them.
 """
 import math
@@ -163,11 +163,39 @@ def sq_threshold(L):
     return t
 
 
-def build_tables(params, cfg, need_acos=True):
+def owl_table(params):
+    """`d2d_plan.owl_tab` (include/d2d.h D2D_OWL_T_*): the constants of yaw_planner.Owl, each evaluated with the reference's own
+    expression (yaw_planner.py:156-161, :178, :204, :215, :220-222)."""
+    p = params
+    top = p.drone_max_yaw_speed
+    hold_dt = 0.8                                                                # Owl.dt
+    u_space = np.arange(-top, top, top / 10)                                     # :161
+    if len(u_space) != A.OWL_NRATE:
+        raise NotImplementedError(f'Owl on the device: np.arange(-w, w, w / 10) has {len(u_space)} entries for '
+                                  f'drone_max_yaw_speed {top!r}, the stage holds {A.OWL_NRATE}')
+    hold = int(hold_dt // p.dt) - 1                                              # :220
+    if hold < 0:
+        raise NotImplementedError(f'Owl on the device: dt {p.dt!r} gives int(0.8 // dt) - 1 = {hold} < 0 calls that repeat a decision')
+    tab = np.zeros(A.OWL_TAB_LEN, dtype=np.float64)
+    for i in range(A.OWL_NRATE):
+        tab[A.OWL_T_RATE + i] = u_space[i]
+        tab[A.OWL_T_RATE08 + i] = (u_space * hold_dt)[i]                         # :204
+        tab[A.OWL_T_TURN + i] = abs(math.radians(u_space[i] * hold_dt))          # :215
+        tab[A.OWL_T_ACT + i] = u_space[i] / top                                  # :222
+    for i, d_i in enumerate(np.arange(0, 360, 10)):                              # :177-178
+        tab[A.OWL_T_DIR + 2 * i], tab[A.OWL_T_DIR + 2 * i + 1] = math.cos(math.radians(d_i)), math.sin(math.radians(d_i))
+    tab[A.OWL_T_FOV], tab[A.OWL_T_DEPTH], tab[A.OWL_T_HOLD] = p.drone_view_range, p.drone_view_depth, hold
+    return tab
+
+
+def build_tables(params, cfg, need_acos=True, owl=False):
     """Scalars + numpy tables of `d2d_plan`, each computed as the reference computes it.  `need_acos`: the arccos decision
-    window of the Oxford stage (view ranges it cannot describe only matter when that stage runs)."""
+    window of the Oxford stage (view ranges it cannot describe only matter when that stage runs).  `owl`: the table of the Owl
+    stage (`owl_tab`), built only when that stage runs (it refuses parameters the stage does not hold)."""
     p = params
     t = {}
+    if owl:
+        t['owl_tab'] = owl_table(p)
     # Primitive.__init__, traj_planner.py:95-107
     if p.drone_max_speed <= 40:
         u_space = np.arange(-p.drone_max_acceleration, p.drone_max_acceleration, 0.4 * p.drone_max_speed - 5)
@@ -227,10 +255,13 @@ class PluginState:
     def __init__(self, params, cfg, device, tracker_radius, planner='Primitive', gaze='Oxford', tables=None):
         self.cfg = cfg
         self.device = torch.device(device)
-        sc, tb = tables if tables is not None else build_tables(params, cfg, need_acos=(gaze == 'Oxford'))
+        sc, tb = tables if tables is not None else build_tables(params, cfg, need_acos=(gaze == 'Oxford'), owl=(gaze == 'Owl'))
+        if gaze == 'Owl' and 'owl_tab' not in tb:
+            tb = dict(tb, owl_tab=owl_table(params))
         self.scalars, self.tables_np = sc, tb
         self.planner = A.PLAN_PRIMITIVE if planner == 'Primitive' else A.PLAN_NONE
-        self.gaze = {'Oxford': A.GAZE_OXFORD, 'LookAhead': A.GAZE_LOOKAHEAD, 'LookGoal': A.GAZE_LOOKGOAL}.get(gaze, A.GAZE_NONE)
+        self.gaze = {'Oxford': A.GAZE_OXFORD, 'LookAhead': A.GAZE_LOOKAHEAD, 'LookGoal': A.GAZE_LOOKGOAL,
+                     'Owl': A.GAZE_OWL}.get(gaze, A.GAZE_NONE)
         B, N = cfg.B, cfg.N
         dev = self.device
         self.tables = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in tb.items()}
@@ -241,6 +272,8 @@ class PluginState:
                       trk_prev=z((B, max(N, 1)), u8), trk_lim=z((B, max(N, 1)), f64), seen_step=z((B, cfg.W, cfg.H), i32),
                       nodes=z((B, sc['node_cap'], A.NODE_F), f64), hash=z((B, sc['hash_cap']), i32),
                       launch_args=z((A.LAUNCH_ARGS_BYTES,), u8), plan_stat=z((B, 4), i32))
+        if self.gaze == A.GAZE_OWL:
+            self.t['owl_state'] = z((B, A.OWL_STATE_F), f64)      # Owl.U_list, the held rate, calls left: a fresh policy is all zero
         r0 = torch.as_tensor(np.asarray(tracker_radius, dtype=np.float64)).reshape(B, -1)
         self.trk_radius0 = z((B, max(N, 1)), f64)
         if N:
@@ -255,12 +288,18 @@ class PluginState:
                 setattr(s, k, self.scalars[k])
         s.planner, s.gaze = self.planner, self.gaze
         for k in A.PLAN_TABLES:
-            setattr(s, k, self.tables[k].data_ptr())
+            setattr(s, k, self.tables[k].data_ptr() if k in self.tables else None)     # owl_tab: only with the Owl stage
         for k in A.PLAN_STATE:
-            setattr(s, k, self.t[k].data_ptr())
+            setattr(s, k, self.t[k].data_ptr() if k in self.t else None)               # owl_state: likewise
         return s
 
     # host views used by the gym facade / tests
+    def owl_scores(self, e):
+        """Owl.U_list of env e: the 36 ten-degree direction scores after the latest decision."""
+        if 'owl_state' not in self.t:
+            raise RuntimeError("owl_scores() needs gaze='Owl'")
+        return self.t['owl_state'][e, :A.OWL_NDIR].cpu().numpy().copy()
+
     def trajectory(self, e):
         """Remaining waypoints of env e as (positions [n, 2], velocities [n, 2])."""
         head, stored = (int(v) for v in self.t['traj_hdr'][e].cpu())

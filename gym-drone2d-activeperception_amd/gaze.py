@@ -13,7 +13,9 @@ mirrors to the host (velocity, yaw; the stored trajectory and the drone's map), 
 host with the same libm calls as the reference (`math.atan2`, `math.degrees`, float `%`) -- the facade's path and the
 oracle's; batches run the same two policies as device gaze stages (`VecDrone2DEnv(..., device_plugins=True,
 gaze='LookAhead' / 'LookGoal')`, `runner.ExperimentBatch`; csrc/d2d_atan2.h returns math.atan2's bits).  `Owl` (36
-direction scores and 20 candidate yaw rates per decision, one decision every 0.8 s) is a host policy only.  Any other policy (the reference's `Oxford` as a
+direction scores and 20 candidate yaw rates per decision, one decision every 0.8 s) is the facade's host policy in the same
+way and the device stage `gaze='Owl'` for batches (csrc/d2d_plugins.h `owl_gaze_env`; csrc/d2d_pow2.h returns the bits of the
+libm pow behind its `** 2`).  Any other policy (the reference's `Oxford` as a
 host object, a user's class) is a host plugin too: it reads the env through the `info` proxies; names this registry
 does not know resolve through the reference's `yaw_planner` module when that is importable.
 """

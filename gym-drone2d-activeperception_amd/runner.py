@@ -63,7 +63,7 @@ class Experiment:
 class ExperimentBatch:
     """The reference's sweep of episodes (`main.py:26-57`: the same cfg over many map ids, one Experiment and one
     CSV row each) as ONE device batch: env i is the world of `map_id + i`, the gaze policy and the planner run on
-    the device (Oxford / LookAhead / LookGoal / Primitive), every env plays exactly one episode (`D2D_DONE_FREEZE`)
+    the device (Oxford / LookAhead / LookGoal / Owl / Primitive), every env plays exactly one episode (`D2D_DONE_FREEZE`)
     and `rows()` returns the reference's CSV rows.  Everything an episode needs stays on the GPU; the host only reads
     the rows.
 
@@ -72,19 +72,23 @@ class ExperimentBatch:
     without that stage (`supports_device_heading_gaze`, e.g. the CPU oracle) LookAhead runs from the host instead: every
     step pulls the drone's velocity and yaw, evaluates the policy with the host's libm and uploads the actions -- one
     launch per step instead of one per episode; LookGoal is refused there.  `device_gaze=False` takes that host path for
-    LookAhead on any backend (A/B measurements)."""
+    LookAhead on any backend (A/B measurements).  `Owl` (yaw_planner.py:151-222) runs as a device gaze stage too and is refused
+    on a backend without it (`supports_device_owl_gaze`)."""
 
     def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_gaze=True):
         from .vec_env import VecDrone2DEnv, build_worlds
         from ._lib import HipBackend
         p = with_defaults(params)
-        if p.gaze_method not in ('Oxford', 'Rotating', 'NoControl', 'LookAhead', 'LookGoal') or p.planner not in ('Primitive', 'NoMove'):
-            raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / LookAhead / LookGoal / Rotating '
-                                      '/ NoControl, planner Primitive / NoMove (use Experiment, one episode at a time, for other '
-                                      'host plugin classes)')
+        if p.gaze_method not in ('Oxford', 'Rotating', 'NoControl', 'LookAhead', 'LookGoal', 'Owl') or p.planner not in ('Primitive', 'NoMove'):
+            raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / LookAhead / LookGoal / Owl / '
+                                      'Rotating / NoControl, planner Primitive / NoMove (use Experiment, one episode at a time, for '
+                                      'other host plugin classes)')
         device_heading = device_gaze and getattr(backend if backend is not None else HipBackend, 'supports_device_heading_gaze', False)
         if p.gaze_method == 'LookGoal' and not device_heading:
             raise NotImplementedError('ExperimentBatch: LookGoal needs a backend with the device LookAhead / LookGoal stage')
+        if p.gaze_method == 'Owl' and not getattr(backend if backend is not None else HipBackend, 'supports_device_owl_gaze', False):
+            raise NotImplementedError('ExperimentBatch: Owl needs a backend with the device Owl stage (use Experiment with the host '
+                                      'policy gaze.Owl, one episode at a time)')
         self._host_lookahead = p.gaze_method == 'LookAhead' and not device_heading
         if p.gaze_method == 'NoControl':
             p.drone_view_range = 360                                   # experiment.py:28-29

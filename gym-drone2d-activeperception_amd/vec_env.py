@@ -12,7 +12,8 @@ Planner modes
   'Primitive' with `device_plugins=True`: traj_planner.py:78-233 runs on the device between the two halves of
               the step; with `gaze='Oxford'` yaw_planner.py:41-127 supplies the action on the device as well
               (`closed_loop()`: gaze -> perceive -> plan -> act, no host round trip); `gaze='LookAhead'` / `'LookGoal'`
-              (yaw_planner.py:18-39 / :225-257) run on the device the same way on a backend that has them
+              (yaw_planner.py:18-39 / :225-257) and `gaze='Owl'` (:151-222) run on the device the same way on a backend
+              that has them
 """
 import numpy as np
 import torch
@@ -100,16 +101,23 @@ class VecDrone2DEnv:
         if device_plugins:
             from .device_plugins import PluginState
             gaze = gaze if gaze is not None else self.params.gaze_method
-            if planner not in ('Primitive', 'NoMove') or gaze not in ('Oxford', 'LookAhead', 'LookGoal', 'Rotating', 'NoControl',
+            if planner not in ('Primitive', 'NoMove') or gaze not in ('Oxford', 'LookAhead', 'LookGoal', 'Owl', 'Rotating', 'NoControl',
                                                                       'external', None):
                 raise NotImplementedError(f'device plugins: planner {planner!r} / gaze {gaze!r} '
-                                          '(device: Primitive, NoMove / Oxford, LookAhead, LookGoal, Rotating, NoControl)')
+                                          '(device: Primitive, NoMove / Oxford, LookAhead, LookGoal, Owl, Rotating, NoControl)')
             # LookAhead / LookGoal (yaw_planner.py:18-39, :225-257) call math.atan2: only a backend with the bit-exact device
             # restatement runs them as a gaze stage (under NoMove LookGoal sees no trajectory and returns 0, as the reference does)
             if gaze in ('LookAhead', 'LookGoal') and not getattr(self.backend, 'supports_device_heading_gaze', False):
                 raise NotImplementedError(f'device plugins: gaze {gaze!r} needs a backend with the device LookAhead / LookGoal stage '
                                           f'({getattr(self.backend, "name", type(self.backend).__name__)} has none); drive the '
                                           "policy from the host with gaze='external' and gaze.LookAhead / gaze.LookGoal")
+            # Owl (yaw_planner.py:151-222) needs libm's pow(x, 2.0) bit for bit as well, and its own per-env state
+            if gaze == 'Owl' and not getattr(self.backend, 'supports_device_owl_gaze', False):
+                raise NotImplementedError(f"device plugins: gaze 'Owl' needs a backend with the device Owl stage "
+                                          f'({getattr(self.backend, "name", type(self.backend).__name__)} has none); drive the '
+                                          "policy from the host with gaze='external' and gaze.Owl")
+            if gaze == 'Owl' and not kf_enabled:
+                raise ValueError("device plugins: gaze 'Owl' reads the Kalman trackers (kf_enabled=True)")
             self.plugins = PluginState(self.params, self.cfg, self.device, self.tracker_radius.numpy(),
                                        planner=planner, gaze=gaze or 'external')
             self._plan = self.plugins.struct()

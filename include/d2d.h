@@ -58,6 +58,26 @@ extern "C" {
                                 main.py:10's default policy it replaces); needs plan.yaw_rate_max > 0                    */
 #define D2D_GAZE_LOOKGOAL 3  /* yaw_planner.py:225-257 on device: turn towards the first remaining waypoint in an UNEXPLORED
                                 cell of the drone's map, else the last one; needs traj / traj_hdr and yaw_rate_max > 0 */
+/* (4 is unassigned: a value the library refuses) */
+#define D2D_GAZE_OWL 5       /* yaw_planner.py:151-222 on device: 36 direction scores, 20 candidate yaw rates, one decision held for
+                                owl_tab[D2D_OWL_T_HOLD] further calls; needs owl_tab, owl_state, the Kalman trackers (kf) and
+                                yaw_rate_max > 0 */
+
+/* Owl: layout of d2d_plan.owl_tab (doubles, D2D_OWL_TAB_LEN of them) and of one env's record of d2d_plan.owl_state */
+#define D2D_OWL_NRATE 20      /* len(Owl.u_space) */
+#define D2D_OWL_NDIR 36       /* len(Owl.U_list) */
+#define D2D_OWL_T_RATE 0      /* [20] u_space[i]                                      */
+#define D2D_OWL_T_RATE08 20   /* [20] u_space[i] * 0.8                                */
+#define D2D_OWL_T_TURN 40     /* [20] abs(radians(u_space[i] * 0.8))                  */
+#define D2D_OWL_T_ACT 60      /* [20] u_space[i] / drone_max_yaw_speed: the action    */
+#define D2D_OWL_T_DIR 80      /* [36][2] cos(radians(d)), sin(radians(d)), d = 0, 10 .. 350 */
+#define D2D_OWL_T_FOV 152     /* theta_h = drone_view_range (degrees)                 */
+#define D2D_OWL_T_DEPTH 153   /* drone_view_depth                                     */
+#define D2D_OWL_T_HOLD 154    /* int(0.8 // dt) - 1 >= 0: calls that repeat a decision */
+#define D2D_OWL_TAB_LEN 160
+#define D2D_OWL_STATE_F 40    /* doubles per env in owl_state */
+#define D2D_OWL_S_RATE 36     /* the held yaw rate u_space[idx] (deg / s)             */
+#define D2D_OWL_S_LEFT 37     /* len(Owl.u): calls left that repeat it                */
 
 /* agent field planes of d2d_state.agents: [B][D2D_AF][N] */
 #define D2D_AF 6
@@ -223,6 +243,10 @@ typedef struct d2d_state {
  *                             every q above the window is inside the cone, every q below outside.  numpy's
  *                             arccos is a SIMD routine that differs from libm by an ulp; the window is how the
  *                             host hands its own arccos to the device (yaw_planner.py:77).
+ *   owl_tab   [D2D_OWL_TAB_LEN] Owl's constants at the D2D_OWL_T_* offsets: u_space = np.arange(-w, w, w / 10) (yaw_planner.py:161),
+ *                             u_space * 0.8 (:204), abs(radians(u_space[i] * 0.8)) (:215), u_space / w (:222), the 36 pairs
+ *                             cos(radians(d)), sin(radians(d)) of :178, theta_h, drone_view_depth and the number of calls a
+ *                             decision is repeated for, int(0.8 // dt) - 1 (:220)
  * ------------------------------------------------------------------------------------------- */
 typedef struct d2d_plan {
   int32_t planner;  /* D2D_PLAN_* */
@@ -266,6 +290,7 @@ typedef struct d2d_plan {
                                 then (dst, left, right) per addition; ids 0..pw_nleaf-1 are the blocks (device only) */
   const int32_t D2D_AS *pw_rowleaf; /* [W] the block that holds the first cell of grid row i (device only) */
   const double D2D_AS *trk_radius0; /* [B][N] tracker radii of the initial world: the reset source of trk_radius */
+  const double D2D_AS *owl_tab;     /* [D2D_OWL_TAB_LEN] Owl's constants (above), or NULL unless gaze == D2D_GAZE_OWL (the oracle ignores it) */
   /* ---- per-env plugin state (read + written) ---- */
   double D2D_AS *traj;         /* [B][traj_cap][4] planner.trajectory: position(2), velocity(2); accelerations are 0 */
   int32_t D2D_AS *traj_hdr;    /* [B][2] index of the head waypoint, number of waypoints stored (len = stored - head) */
@@ -293,6 +318,10 @@ typedef struct d2d_plan {
   /* ---- diagnostics ---- */
   int32_t D2D_AS *plan_stat;   /* [B][4] searches run, expansions of the last search, nodes of the last search,
                            capacity overflow flag (sticky; a search that overflowed reports failure) */
+  /* ---- per-env plugin state of the Owl gaze stage (read + written) ---- */
+  double D2D_AS *owl_state;    /* [B][D2D_OWL_STATE_F] Owl.U_list (36 scores), the held yaw rate, the calls left that repeat it, 2 spare;
+                           all zero = a fresh policy (d2d_plan_reset, auto-reset).  NULL unless gaze == D2D_GAZE_OWL (the oracle
+                           ignores it) */
 } d2d_plan;
 
 /* one search node = D2D_NODE_F doubles: position(2), velocity(2), cost, total_cost, acc(2), then parent slot / itr /
@@ -360,7 +389,9 @@ int d2d_tan_array(const double *in, double *out, int64_t n, void *stream);
 /* policy.plan(info) of the gaze plugin for every env (experiment.py:69), run BEFORE the step on the state the
  * previous step left: writes st->action.  D2D_GAZE_OXFORD: yaw_planner.py:81-127 (view map of the current pose,
  * time-since-observed map, swept-trajectory reward, 6 yaw-rate candidates).  D2D_GAZE_LOOKAHEAD / D2D_GAZE_LOOKGOAL:
- * yaw_planner.py:28-39 / :225-257 (a heading by Python's math.atan2, one clipped yaw rate).  D2D_GAZE_NONE: no-op. */
+ * yaw_planner.py:28-39 / :225-257 (a heading by Python's math.atan2, one clipped yaw rate).  D2D_GAZE_OWL: yaw_planner.py:187-222
+ * (direction scores, 20 candidate yaw rates every 0.8 s; libm's pow(x, 2.0) bit for bit) -- with it every --gaze_method of the
+ * reference runs on the device.  D2D_GAZE_NONE: no-op. */
 int d2d_gaze_stage(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan, void *stream);
 
 /* planner.replan_check(drone) + planner.plan(drone, dt) (envs/drone_v2.py:194-197) + the head waypoint
@@ -379,7 +410,7 @@ int d2d_plan_stage(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan
 int d2d_closed_loop(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan, int32_t nsteps,
                     int32_t on_done, const d2d_state *init, void *stream);
 
-/* Clears the plugin state (trajectory, tracker radii <- plan->trk_radius0, seen map) of the envs with
+/* Clears the plugin state (trajectory, tracker radii <- plan->trk_radius0, seen map, Owl's scores and held decision) of the envs with
  * mask[e * mask_stride] != 0 (mask == NULL: all): Experiment.__init__ builds fresh plugin objects per episode
  * (experiment.py:31-34). */
 int d2d_plan_reset(const d2d_cfg *cfg, const d2d_plan *plan, const uint8_t *mask, int32_t mask_stride,

@@ -18,6 +18,11 @@ extern "C" {
  * FMA variant.  Returns 0, or a negative error like every entry point. */
 int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, void *stream);
 
+/* Device restatement of the host libm pow(x, 2.0) that numpy's `float64 ** 2` resolves to in the Owl gaze stage
+ * (yaw_planner.py:209): out[i] = pow(x[i], 2.0), bit-for-bit glibc 2.35 x86-64 FMA variant (not x * x).  Returns 0, or a
+ * negative error like every entry point. */
+int d2d_pow2_array(const double *x, double *out, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
