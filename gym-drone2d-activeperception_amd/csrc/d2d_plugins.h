@@ -277,6 +277,11 @@ __device__ unsigned long long d2d_search_prof[16];
 #define SP_FLUSH() do { } while (0)
 #endif
 
+template <int N>
+struct IntC {  // a compile-time int as a function argument
+  static constexpr int value = N;
+};
+
 struct SearchLds {
   int *chain;       // [128] path slots; during the search: the 64-bucket table of the successors' keys (de-duplication)
   double *us;       // [nu] u_space
@@ -562,100 +567,20 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
         ax = S.us[ia];
         ay = S.us[ja];
       }
-      const double hx = ax / 2, hy = ay / 2;
-      const double vex = vx + (2 * H) * hx, vey = vy + (2 * H) * hy;  // :172,183
+      double hx = ax / 2, hy = ay / 2;
+      double vex = vx + (2 * H) * hx, vey = vy + (2 * H) * hy;  // :172,183
       ok = ok && (__builtin_fma(vey, vey, vex * vex) <= vmax2);
-      // :175-180.  Few primitives pass the speed limit (about ten of 64), so the collision samples are spread over
-      // the lanes as (primitive, sample) pairs instead of one sample round per iteration: the reference's early
-      // `break` only skips work, a successor needs ALL its samples free.
-      const unsigned long long vm = __ballot(ok);
-      const int myrank = __popcll(vm & lt_mask);
       SP_T(sp3);
       SP_ADD(2, sp2, sp3);
-      {
-        // the accelerations of the primitives that passed, by rank: the pairs fetch theirs with one LDS read
-        const int nv = __popcll(vm);
-        double *rax = S.rv, *ray = (double *)S.rk;
-        if (ok) {
-          rax[myrank] = hx;
-          ray[myrank] = hy;
-        }
-        wave_sync_lds();
-        const int npair = nv * p.n_sample;
-        const int my_lo = myrank * p.n_sample;  // this primitive's pairs: [my_lo, my_lo + n_sample)
-        int nfree = 0;
-        // two rounds of pairs in flight (about ten primitives x eight samples = 80 pairs); which samples are free comes back as
-        // ballots: every primitive counts the set bits of its own pairs -- no LDS counters, no hand-off
-        for (int q0 = 0; q0 < npair; q0 += 2 * WAVE) {
-          int pr[2], si[2];
-          bool in[2], fr[2];
-          double sxv[2], syv[2], tgv[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int q = q0 + u * WAVE + lane;
-            in[u] = q < npair;
-            fd_ns.divmod(in[u] ? q : 0, pr[u], si[u]);
-          }
-          double shx[2], shy[2], tt[2], tt2[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            shx[u] = rax[pr[u]]; shy[u] = ray[pr[u]]; tt[u] = S.st[2 * si[u]]; tt2[u] = S.st[2 * si[u] + 1];
-          }
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const double sx = rint(__builtin_fma(tt2[u], shx[u], px + tt[u] * vx)), sy = rint(__builtin_fma(tt2[u], shy[u], py + tt[u] * vy));
-            const double tg = tt[u] + (double)citr * H;
-            sxv[u] = sx; syv[u] = sy; tgv[u] = tg;
-          }
-          if (fits_all) {  // wave-uniform: integer probes
-            // walls and trackers of both rounds without a branch between them (`&`, not `&&`): a short-circuit costs an exec-mask
-            // branch per round and keeps the second round's loads from overlapping the first one's arithmetic
-            bool wall[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              const int xi = (int)sxv[u], yi = (int)syv[u];
-              if (rows) {
-                // outside the map = wall whatever the row says: only the row index has to stay inside the table
-                const bool inside = ((unsigned int)xi < (unsigned int)wpx_i) & ((unsigned int)yi < (unsigned int)hpx_i);
-                unsigned int ci = __umul24((unsigned int)xi, 52429u) >> 19;
-                ci = ci < 63u ? ci : 63u;
-                const unsigned int cj = (__umul24((unsigned int)yi, 52429u) >> 19) & 63u;
-                wall[u] = !inside | (((S.prow[ci] >> cj) & 1ull) != 0ull);
-              } else {
-                wall[u] = plan_wall_int(c, dm, xi, yi, safe_i, wpx_i, hpx_i);
-              }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) fr[u] = !wall[u] & !plan_hits_tracker(T, sxv[u], syv[u], tgv[u]);
-          } else {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) fr[u] = plan_is_free(c, p, dm, T, sxv[u], syv[u], tgv[u], inv_scale);
-          }
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const unsigned long long fm = __ballot(in[u] & fr[u]);
-            const int qb = q0 + u * WAVE;  // this round holds the pairs [qb, qb + 64)
-            if (ns_pow2) {
-              const unsigned int sh = (unsigned int)(my_lo - qb);
-              if (sh < (unsigned int)WAVE) nfree = __popcll(p.n_sample >= WAVE ? fm : ((fm >> sh) & ((1ull << p.n_sample) - 1ull)));
-            } else {
-              const int lo = max(my_lo, qb) - qb, hi = min(my_lo + p.n_sample, qb + WAVE) - qb;
-              if (hi > lo) {
-                const unsigned long long w = fm >> lo;
-                nfree += __popcll(hi - lo >= WAVE ? w : (w & ((1ull << (hi - lo)) - 1ull)));
-              }
-            }
-          }
-        }
-        if (ok) ok = nfree == p.n_sample;
-      }
-      SP_T(sp4);
-      SP_ADD(3, sp3, sp4);
-      const double ex = rint((px + H * vx) + (H * H) * hx), ey = rint((py + H * vy) + (H * H) * hy);  // :182
+      // ---- :192-206 BEFORE :175-186.  The reference tests a successor's samples first and consults the dict afterwards; is_free has
+      // no side effect, so the order is free, and a successor the dict discards (its key closed, or open at no higher cost) needs
+      // no sample at all.  Filtering against the dict as it stands BEFORE the expansion is exact also where two successors of one
+      // node share a key: during an expansion a closed node stays closed and an open node's cost only goes down, so what the dict
+      // rejects now it rejects in generation order too, and a rejected successor changes nothing another one sees.
+      double ex = rint((px + H * vx) + (H * H) * hx), ey = rint((py + H * vy) + (H * H) * hy);  // :182
       const double cost = ccost + S.pc[ok ? pi : 0] + 10;                                             // :184, the term from its table
       const long long key = node_key(ex, ey, vex, vey);
       const unsigned int h32 = key_hash(key);
-      // ---- :192-202 for all successors of the batch at once ----
       int slot = -1;
       int slot_state = 0;  // state and cost of the node found, fetched in the same round trip as its key
       double slot_cost = 0.0;
@@ -701,14 +626,146 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
           }
         }
       }
+      const bool exists = slot >= 0;
+      // :198-199, :204.  What stays is new, or open at a higher cost than its own -- hence than the cheapest of its key: the state and
+      // the cost of the node found are settled here, the write below asks for neither.
+      ok = ok && (!exists || ((slot_state != 2) & (slot_cost > cost)));
+      // :175-180.  Few primitives pass the speed limit and the dict (about seven of 64), so the collision samples are spread over
+      // the lanes as (primitive, sample) pairs instead of one sample round per iteration: the reference's early
+      // `break` only skips work, a successor needs ALL its samples free.
+      const unsigned long long vm = __ballot(ok);
+      SP_T(sp4);
+      SP_ADD(3, sp3, sp4);
+      if (vm == 0ull) {
+        // the dict discards every successor of the batch: no samples, no stores, no hand-off through memory -- only the LDS order
+        // (the popped node's +inf in the cost mirror) before the next scan
+        wave_sync_lds();
+#ifdef D2D_SEARCH_PROF
+        spacc[9] += 1;
+        spacc[13] += 1;
+        SP_T(sp8);
+        SP_ADD(8, sp0, sp8);
+#endif
+        continue;
+      }
+      const int myrank = __popcll(vm & lt_mask);
+      {
+        // the accelerations of the primitives that passed, by rank: the pairs fetch theirs with one LDS read
+        const int nv = __popcll(vm);
+        double *rax = S.rv, *ray = (double *)S.rk;
+        if (ok) {
+          rax[myrank] = hx;
+          ray[myrank] = hy;
+        }
+        wave_sync_lds();
+        const int npair = nv * p.n_sample;
+        const int my_lo = myrank * p.n_sample;  // this primitive's pairs: [my_lo, my_lo + n_sample)
+        int nfree = 0;
+        // which samples are free comes back as ballots: every primitive counts the set bits of its own pairs -- no LDS counters, no
+        // hand-off.  NR rounds of 64 pairs in flight, starting at pair q0.
+        auto pair_rounds = [&](auto nr_c, const int q0) __attribute__((always_inline)) {
+          constexpr int NR = decltype(nr_c)::value;
+          int pr[NR], si[NR];
+          bool in[NR], fr[NR];
+          double sxv[NR], syv[NR], tgv[NR];
+#pragma unroll
+          for (int u = 0; u < NR; ++u) {
+            const int q = q0 + u * WAVE + lane;
+            in[u] = q < npair;
+            fd_ns.divmod(in[u] ? q : 0, pr[u], si[u]);
+          }
+          double shx[NR], shy[NR], tt[NR], tt2[NR];
+#pragma unroll
+          for (int u = 0; u < NR; ++u) {
+            shx[u] = rax[pr[u]]; shy[u] = ray[pr[u]]; tt[u] = S.st[2 * si[u]]; tt2[u] = S.st[2 * si[u] + 1];
+          }
+#pragma unroll
+          for (int u = 0; u < NR; ++u) {
+            const double sx = rint(__builtin_fma(tt2[u], shx[u], px + tt[u] * vx)), sy = rint(__builtin_fma(tt2[u], shy[u], py + tt[u] * vy));
+            const double tg = tt[u] + (double)citr * H;
+            sxv[u] = sx; syv[u] = sy; tgv[u] = tg;
+          }
+          if (fits_all) {  // wave-uniform: integer probes
+            // walls and trackers of both rounds without a branch between them (`&`, not `&&`): a short-circuit costs an exec-mask
+            // branch per round and keeps the second round's loads from overlapping the first one's arithmetic
+            bool wall[NR];
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+              const int xi = (int)sxv[u], yi = (int)syv[u];
+              if (rows) {
+                // outside the map = wall whatever the row says: only the row index has to stay inside the table
+                const bool inside = ((unsigned int)xi < (unsigned int)wpx_i) & ((unsigned int)yi < (unsigned int)hpx_i);
+                unsigned int ci = __umul24((unsigned int)xi, 52429u) >> 19;
+                ci = ci < 63u ? ci : 63u;
+                const unsigned int cj = (__umul24((unsigned int)yi, 52429u) >> 19) & 63u;
+                wall[u] = !inside | (((S.prow[ci] >> cj) & 1ull) != 0ull);
+              } else {
+                wall[u] = plan_wall_int(c, dm, xi, yi, safe_i, wpx_i, hpx_i);
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < NR; ++u) fr[u] = !wall[u] & !plan_hits_tracker(T, sxv[u], syv[u], tgv[u]);
+          } else {
+#pragma unroll
+            for (int u = 0; u < NR; ++u) fr[u] = plan_is_free(c, p, dm, T, sxv[u], syv[u], tgv[u], inv_scale);
+          }
+#pragma unroll
+          for (int u = 0; u < NR; ++u) {
+            const unsigned long long fm = __ballot(in[u] & fr[u]);
+            const int qb = q0 + u * WAVE;  // this round holds the pairs [qb, qb + 64)
+            if (ns_pow2) {
+              const unsigned int sh = (unsigned int)(my_lo - qb);
+              if (sh < (unsigned int)WAVE) nfree = __popcll(p.n_sample >= WAVE ? fm : ((fm >> sh) & ((1ull << p.n_sample) - 1ull)));
+            } else {
+              const int lo = max(my_lo, qb) - qb, hi = min(my_lo + p.n_sample, qb + WAVE) - qb;
+              if (hi > lo) {
+                const unsigned long long w = fm >> lo;
+                nfree += __popcll(hi - lo >= WAVE ? w : (w & ((1ull << (hi - lo)) - 1ull)));
+              }
+            }
+          }
+        };
+        // at most 64 pairs left (eight primitives x eight samples; four expansions in ten of a boxed-in search): one round;
+        // else two rounds in flight per trip
+        if (npair <= WAVE) {
+          pair_rounds(IntC<1>{}, 0);
+#ifdef D2D_SEARCH_PROF
+          spacc[14] += 1;
+#endif
+        } else {
+          for (int q0 = 0; q0 < npair; q0 += 2 * WAVE) pair_rounds(IntC<2>{}, q0);
+        }
+        if (ok) ok = nfree == p.n_sample;
+      }
       SP_T(sp5);
       SP_ADD(4, sp4, sp5);
+      // The end state is formed again from the accelerations (ten operations) instead of living through the pair stage in eight
+      // registers: the kernel has none to spare (the empty asm keeps the compiler from reusing the first copy).  The key above was
+      // hashed from the first copy, the record below is stored from this one: the two are the same bits because both are the same
+      // expressions under -ffp-contract=off (csrc/build.sh) -- with contraction on, the compiler could fuse one copy and not the
+      // other, and a record's position would part from its key.
+      asm volatile("" : "+v"(ax), "+v"(ay));
+      hx = ax / 2;
+      hy = ay / 2;
+      vex = vx + (2 * H) * hx;
+      vey = vy + (2 * H) * hy;
+      ex = rint((px + H * vx) + (H * H) * hx);
+      ey = rint((py + H * vy) + (H * H) * hy);
       // the successors among themselves (rank order = lane order = generation order): the first lane of a key owns its
       // place in the dict, the cheapest (earliest on ties) its value.  Repeats within one expansion are rare:
       // every successor puts its key into a 64-bucket LDS table (the path buffer, free at this point) by compare-and-swap:
       // finding its own key there = a repeat; another key = next bucket.  One or two LDS round trips for ten keys, and exact:
       // the resolution below runs only when two successors really share a key (or a key equals the empty marker, 0)
       const unsigned long long m = __ballot(ok);
+      if (m == 0ull) {  // no successor is collision-free: nothing to write either
+        wave_sync_lds();
+#ifdef D2D_SEARCH_PROF
+        spacc[9] += 1;
+        SP_T(sp8);
+        SP_ADD(8, sp0, sp8);
+#endif
+        continue;
+      }
       const int nok = __popcll(m), rank = __popcll(m & lt_mask);
       unsigned long long dupm = 0;
       if (!nodup) {
@@ -756,9 +813,6 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
       SP_T(sp6);
       SP_ADD(5, sp5, sp6);
       const bool is_leader = ok && leader == lane;
-      const bool exists = slot >= 0;
-      const bool closed = exists & (slot_state == 2);
-      const double ecost = slot_cost;
       const unsigned long long newm = __ballot(is_leader && !exists);
       const int nnew = __popcll(newm);
       if (nn + nnew > p.node_cap) {
@@ -768,7 +822,7 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
       int myslot = slot;
       if (is_leader && !exists) myslot = nn + __popcll(newm & lt_mask);
       const int gslot = dupm != 0ull ? __shfl(myslot, leader, WAVE) : myslot;  // the slot of my group (no repeats: my own)
-      const bool write = ok && wlane == lane && (!exists || (!closed && ecost > wcost));
+      const bool write = ok && wlane == lane;  // the cheapest of its key (earliest on ties); the dict has agreed above
       if (write) {
         double *rw = nd.rec(gslot);
         const double tot = cost + 0.5 * norm2(ex - tx, ey - ty) + 0.1 * norm2(vex, vey);

@@ -76,20 +76,25 @@ def main():
     # kernel metadata: name -> vgpr / sgpr / spills / scratch
     meta = {}
     cur = {}
+    agpr = '?'
     for ln in notes.splitlines():
         m = re.match(r'\s*-?\s*\.(\w+):\s*(.*)', ln)
         if not m:
             continue
         k, v = m.group(1), m.group(2).strip().strip("'")
-        if k == 'agpr_count' and cur.get('name'):
-            pass
+        if k == 'agpr_count':  # a kernel's first key (they are sorted): it comes BEFORE the kernel's name and closes the one before
+            if cur.get('name') and cur.get('vgpr_count') is not None:
+                meta[cur['name']] = cur
+                cur = {}
+            agpr = v
+            continue
         if k in ('name', 'vgpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size',
-                 'group_segment_fixed_size', 'agpr_count'):
+                 'group_segment_fixed_size'):
             if k == 'name' and 'symbol' not in cur and cur.get('name') and cur.get('vgpr_count') is not None:
                 meta[cur['name']] = cur
                 cur = {}
             if k == 'name' and v.startswith('_Z'):
-                cur = {'name': v}
+                cur = {'name': v, 'agpr_count': agpr}
             elif k != 'name':
                 cur[k] = v
     if cur.get('name'):

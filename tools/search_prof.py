@@ -21,7 +21,8 @@ TRACE = sys.argv[2] if len(sys.argv) > 2 else 'deadlock_primitive'
 R = replay.Replay(pkg, be, TRACE, kf=True, copies=B)
 ps = DP.PluginState(R.p, R.cfg, be.device, [R.world['tracker_radius']] * B, planner='Primitive', gaze='external')
 plan = ps.struct()
-names = ['argmin', 'cur fields', 'speed filter', 'is_free pairs', 'key + probe', 'dedup', 'exists + writes', 'fence', 'TOTAL', 'batches']
+# the expansion's sections in their order: the dict is consulted BEFORE the collision samples (csrc/d2d_plugins.h, plan_search)
+names = ['argmin', 'cur fields', 'speed filter', 'key + probe + dict filter', 'is_free pairs', 'dedup', 'writes', 'fence', 'TOTAL', 'batches']
 for t in range(int(sys.argv[3]) if len(sys.argv) > 3 else 4):
     s = R.st.struct()
     R.st.action.fill_(float(R.fx['t_action'][t]))
@@ -36,3 +37,6 @@ for t in range(int(sys.argv[3]) if len(sys.argv) > 3 else 4):
         continue
     n = max(1, out[9])
     print(f'step {t + 1} B={B}:', ', '.join(f'{nm} {out[i] / n:.0f}' for i, nm in enumerate(names[:9])), f'(clock ticks per expansion, {out[9]} expansions); per search: setup {out[10]}, path + trajectory {out[11]} ({out[12]} successful)')
+    # the sections behind the dict filter are averaged over ALL batches, the ones that skipped them included
+    print(f'    batches the dict left no successor of (no pair stage, no writes): {out[13]} = {100 * out[13] / n:.1f} %; '
+          f'with at most 64 pairs left (one round): {out[14]} = {100 * out[14] / n:.1f} %')
