@@ -25,6 +25,7 @@ CF = 8
 C_STEPS, C_FAIL, C_SM, C_TGT_NEXT, C_NTGT, C_TRACKED, C_BUF_N, C_BUF_TS = range(8)
 F_COLLISION, F_DEADLOCK, F_FREEZING, F_DONE = range(4)
 KF = 20
+RNG_WORDS, RNG_POS, RNG_NPAIR, RNG_NREGEN = 640, 624, 625, 626   # d2d_state.rng (include/d2d.h D2D_RNG_WORDS)
 
 ST_FSM, ST_AGENTS, ST_RAYCAST, ST_DYNGRID, ST_TRACKER, ST_CONTROL, ST_COLLIDE, ST_OBS = (1 << i for i in range(8))
 ST_PERCEIVE = ST_FSM | ST_AGENTS | ST_RAYCAST | ST_DYNGRID | ST_TRACKER
@@ -45,7 +46,7 @@ class Cfg(C.Structure):
 
 STATE_FIELDS = ('agents', 'agent_unit', 'dyn_prev', 'gt', 'dmap', 'drone', 'target', 'targets', 'counters',
                 'active', 'kf', 'kf_len', 'action', 'plan_ok', 'wp_valid', 'wp', 'noise', 'hit', 'newly',
-                'flags', 'obs_local', 'obs_yaw')
+                'flags', 'obs_local', 'obs_yaw', 'rng', 'rng_draws')
 
 
 class State(C.Structure):
@@ -87,6 +88,8 @@ def bind(lib, prefix='d2d_'):
         'sincos_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         'atan2_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         'pow2_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+        'log_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+        'rng_draw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
         'launch_shape': (C.c_int, [P(Cfg), P(Plan), P(C.c_int32 * 4)]),
     }
     out = {}
@@ -100,8 +103,9 @@ def bind(lib, prefix='d2d_'):
     return out
 
 
-# atan2_array, pow2_array: test hooks of the HIP library alone (include/d2d_hooks.h), outside the surface the oracle mirrors
-OPTIONAL = ('launch_shape', 'atan2_array', 'pow2_array')
-HIP_ONLY_ENTRY_POINTS = ('atan2_array', 'pow2_array')
+# atan2_array, pow2_array, log_array, rng_draw: test hooks of the HIP library alone (include/d2d_hooks.h), outside the surface the
+# oracle mirrors
+OPTIONAL = ('launch_shape', 'atan2_array', 'pow2_array', 'log_array', 'rng_draw')
+HIP_ONLY_ENTRY_POINTS = ('atan2_array', 'pow2_array', 'log_array', 'rng_draw')
 ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_stages', 'rollout', 'reset',
                 'tan_array', 'gaze_stage', 'plan_stage', 'closed_loop', 'plan_reset', 'sincos_array', 'launch_shape')

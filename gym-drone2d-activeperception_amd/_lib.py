@@ -46,6 +46,7 @@ class HipBackend:
     supports_tiled_grids = True      # d2d_cfg.grid_tile = 16 (the CPU oracle keeps the reference's row-major grids)
     supports_device_heading_gaze = True   # d2d_plan.gaze = LookAhead / LookGoal (the CPU oracle runs only Oxford's gaze stage)
     supports_device_owl_gaze = True       # d2d_plan.gaze = Owl
+    supports_device_noise = True          # d2d_state.rng: the tracker stage draws the measurement noise itself (var_cam != 0)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -106,6 +107,13 @@ class HipBackend:
 
     def pow2_array(self, x, out):
         self._chk(self.fn['pow2_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))
+
+    def log_array(self, x, out):
+        self._chk(self.fn['log_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))
+
+    def rng_draw(self, rng, m, out):
+        """rng [B, RNG_WORDS] int32 / uint32 bits, m [B] int32, out [B, max_m, 2] float64"""
+        self._chk(self.fn['rng_draw'](rng.data_ptr(), m.data_ptr(), out.data_ptr(), rng.shape[0], out.shape[1], self._stream()))
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

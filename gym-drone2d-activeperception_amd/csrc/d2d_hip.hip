@@ -50,6 +50,10 @@
 #define D2D_TAN_QUAL __device__ __forceinline__
 #define D2D_TAN_TBL_QUAL __device__ const
 #include "d2d_tan.h"
+#define D2D_LOG_QUAL __device__ __forceinline__
+#define D2D_LOG_TBL_QUAL __device__ const
+#define D2D_RNG_QUAL __device__ __forceinline__
+#include "d2d_rng.h"
 
 #define WAVE 64
 #define WAVES_PER_BLOCK 4
@@ -1296,13 +1300,131 @@ __device__ __forceinline__ void obs_full(const d2d_cfg &c, const d2d_state &s, i
   if (lane == 0) s.obs_yaw[e] = (float)r.yaw;
 }
 
+// ---- the measurement noise's random stream (d2d_state.rng; d2d_rng.h) by one wave ----
+// The next key, in place: 64 words per pass in ascending order, which is the order the sequential algorithm writes them in.  Word i
+// reads words i + 1 (old; the last one reads the new word 0) and i + 397 mod 624 (old below i = 227, new from there on): never a
+// word of its own pass except i + 1, which its neighbour lane replaces -- so a pass reads, then writes, then fences.
+template <typename P>
+__device__ __forceinline__ void rng_wave_regen(P key, int lane) {
+  for (int i0 = 0; i0 < D2D_RNG_KEY; i0 += WAVE) {
+    const int i = i0 + lane;
+    uint32_t v = 0;
+    if (i < D2D_RNG_KEY) {
+      const int i1 = i + 1 == D2D_RNG_KEY ? 0 : i + 1;
+      const int im = i + D2D_RNG_M >= D2D_RNG_KEY ? i + D2D_RNG_M - D2D_RNG_KEY : i + D2D_RNG_M;
+      v = d2d_rng_twist(key[i], key[i1], key[im]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every lane holds its three words before any lane writes one
+    __builtin_amdgcn_wave_barrier();
+    if (i < D2D_RNG_KEY) key[i] = v;
+    wave_sync_global();
+  }
+}
+
+// position of the n-th set bit of m (n = 0: the lowest); m has more than n bits set
+__device__ __forceinline__ int nth_set_bit(unsigned long long m, int n) {
+  int p = 0;
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const int cnt = __popcll((m >> p) & ((1ull << w) - 1ull));
+    if (n >= cnt) {
+      n -= cnt;
+      p += w;
+    }
+  }
+  return p;
+}
+
+// `m` pairs of stream `key` from position `pos` (a multiple of 4, <= 624; updated): every pass a lane evaluates one attempt of
+// the polar method -- attempt j takes words pos + 4 j .. pos + 4 j + 3 whatever the attempts before it decided, and from an aligned
+// position none straddles the end of the key -- and a ballot says which were accepted; the q-th accepted attempt of the call is
+// its q-th pair, handed to emit(q, v0, v1) by the lane that holds it, and the stream ends four words behind the m-th.  Returns the
+// pairs drawn: m, unless `regen` (updated) reached `cap` (d2d_rng_regen_cap: a key that accepts nothing must not hang the wave).
+template <typename P, typename F>
+__device__ __forceinline__ int rng_wave_pairs(P key, int &pos, int &regen, int cap, int m, int lane, F &&emit) {
+  int got = 0;
+  while (got < m) {
+    if (pos >= D2D_RNG_KEY) {
+      if (regen >= cap) break;
+      rng_wave_regen(key, lane);
+      pos = 0;
+      regen += 1;
+    }
+    const int n = min((D2D_RNG_KEY - pos) >> 2, WAVE);
+    bool ok = false;
+    double v0 = 0.0, v1 = 0.0;
+    if (lane < n) {
+      const int w = pos + 4 * lane;
+      ok = d2d_rng_attempt(d2d_rng_temper(key[w]), d2d_rng_temper(key[w + 1]), d2d_rng_temper(key[w + 2]),
+                           d2d_rng_temper(key[w + 3]), &v0, &v1) != 0;
+    }
+    const unsigned long long am = __ballot(ok);
+    const int rank = __popcll(am & ((1ull << lane) - 1ull)), na = __popcll(am), need = m - got;
+    if (ok && rank < need) emit(got + rank, v0, v1);
+    if (na >= need) {
+      pos += 4 * (nth_set_bit(am, need - 1) + 1);
+      got = m;
+    } else {
+      pos += 4 * n;
+      got += na;
+    }
+  }
+  return got;
+}
+
+// the stream's position as the library accepts it (include/d2d.h, d2d_state.rng)
+__device__ __forceinline__ bool rng_pos_ok(int pos) { return (unsigned int)pos <= (unsigned int)D2D_RNG_KEY && (pos & 3) == 0; }
+
+template <typename P>
+__device__ __forceinline__ void rng_wave_store(P st, int pos, int got, int regen, int lane) {
+  if (lane == 0) {
+    st[D2D_RNG_POS] = (uint32_t)pos;
+    st[D2D_RNG_NPAIR] += (uint32_t)got;
+    st[D2D_RNG_NREGEN] += (uint32_t)regen;
+  }
+}
+
+// utils.py:603-605: np.random.randn(2) for every agent the rays hit, in agent order, into rng_draws (0 for the others).  The hit
+// flags are the raycast's, in LDS (this launch's or, staged by run_env, an earlier one's).
+__device__ __forceinline__ void st_noise_draw(const d2d_cfg &c, const d2d_state &s, int e, int lane, const LdsView &L) {
+  const int N = c.N;
+  uint32_t D2D_AS *st = s.rng + (size_t)e * D2D_RNG_WORDS;
+  double D2D_AS *out = s.rng_draws + (size_t)e * N * 2;
+  int pos = __builtin_amdgcn_readfirstlane((int)st[D2D_RNG_POS]);
+  const bool bad = !rng_pos_ok(pos);
+  const double nan = __builtin_nan("");
+  int total = 0, got_all = 0, regen = 0;
+  for (int k0 = 0; k0 < N; k0 += WAVE) total += __popcll(__ballot(k0 + lane < N && L.hit[k0 + lane] != 0));
+  const int cap = d2d_rng_regen_cap(total);
+  for (int k0 = 0; k0 < N; k0 += WAVE) {
+    const int k = k0 + lane;
+    const bool h = k < N && L.hit[k] != 0;
+    const unsigned long long hm = __ballot(h);
+    const int m = __popcll(hm);
+    int got = 0;
+    if (!bad && m > 0)
+      got = rng_wave_pairs(st, pos, regen, cap, m, lane, [&](int q, double v0, double v1) {
+        const int kk = k0 + nth_set_bit(hm, q);
+        out[(size_t)kk * 2] = v0;
+        out[(size_t)kk * 2 + 1] = v1;
+      });
+    got_all += got;
+    if (k < N && (!h || __popcll(hm & ((1ull << lane) - 1ull)) >= got)) {  // not hit: 0; hit but not drawn (a stream refused): NaN
+      out[(size_t)k * 2] = h ? nan : 0.0;
+      out[(size_t)k * 2 + 1] = h ? nan : 0.0;
+    }
+  }
+  if (!bad) rng_wave_store(st, pos, got_all, regen, lane);
+  wave_sync_global();  // the trackers read the draws of other lanes
+}
+
 // ---- Kalman trackers, utils.py:172-275; lane = tracker slot ----
 // F = [[1,0,.1,0],[0,1,0,.1],[0,0,1,0],[0,0,0,1]] and H = [I2 0] are constant, so the dense products
 // of the reference collapse: multiplying by an exact 0 or 1 and adding an exact 0 do not round, hence the
 // sparse expressions below give the same values as the oracle's dense loops (tests compare bit for bit).
 template <bool KF_LDS>
 __device__ __forceinline__ void st_tracker(const d2d_cfg &c, const d2d_state &s, int e, int lane, const Geom &g,
-                                           const LdsView &L, EnvRegs &r, size_t noise_off) {
+                                           const LdsView &L, EnvRegs &r, const double D2D_AS *nz, size_t noise_off) {
   const int N = c.N;
   int arch_n = 0, arch_ts = 0;
   // More than 128 agents: the few trackers that have anything to do (active, or hit this step) are spread over all lane passes,
@@ -1335,9 +1457,9 @@ __device__ __forceinline__ void st_tracker(const d2d_cfg &c, const d2d_state &s,
         double *__restrict__ gk = s.kf + ((size_t)e * N + k) * D2D_KF;
         int len = 1;
         double zx = L.ax[k], zy = L.ay[k];
-        if (s.noise) {
-          zx = zx + c.sigma * s.noise[noise_off + ((size_t)e * N + k) * 2];
-          zy = zy + c.sigma * s.noise[noise_off + ((size_t)e * N + k) * 2 + 1];
+        if (nz) {
+          zx = zx + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2];
+          zy = zy + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2 + 1];
         }
         double m0, m1, m2, m3;
         double S[16];
@@ -1451,7 +1573,7 @@ __device__ __forceinline__ void st_tracker(const d2d_cfg &c, const d2d_state &s,
 // same predicted values -- the updated one (:249-260).  Each element is the expression the sequential code evaluates for it, operand
 // for operand (F and H are 0 / 1 / 0.1: the dense products collapse without changing a rounding), so the state stays bit-identical.
 __device__ __forceinline__ void st_tracker_elem(const d2d_cfg &c, const d2d_state &s, int e, int lane, const Geom &g,
-                                                const LdsView &L, EnvRegs &r, size_t noise_off) {
+                                                const LdsView &L, EnvRegs &r, const double D2D_AS *nz, size_t noise_off) {
   const int N = c.N;
   if (!c.kf_enabled) {
     for (int k = lane; k < N; k += WAVE)
@@ -1512,9 +1634,9 @@ __device__ __forceinline__ void st_tracker_elem(const d2d_cfg &c, const d2d_stat
     int len = act ? klen + 1 : 1;
     if (archive) len = 1;
     double zx = L.ax[k], zy = L.ay[k];
-    if (s.noise) {
-      zx = zx + c.sigma * s.noise[noise_off + ((size_t)e * N + k) * 2];
-      zy = zy + c.sigma * s.noise[noise_off + ((size_t)e * N + k) * 2 + 1];
+    if (nz) {
+      zx = zx + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2];
+      zy = zy + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2 + 1];
     }
     double out;
     if (!act) {  // first sighting, utils.py:263-273 (has_z holds: the tracker is on the list)
@@ -1583,7 +1705,7 @@ __device__ __forceinline__ double quad_bcast_f64(double v) {
 // it, operand for operand (F and H are 0 / 1 / 0.1: the dense products collapse without changing a rounding): bit-identical state.
 template <bool KF_LDS>
 __device__ __forceinline__ void st_tracker_quad(const d2d_cfg &c, const d2d_state &s, int e, int lane, const Geom &g,
-                                                const LdsView &L, EnvRegs &r, size_t noise_off) {
+                                                const LdsView &L, EnvRegs &r, const double D2D_AS *nz, size_t noise_off) {
   const int N = c.N;
   if (!c.kf_enabled) {
     for (int k = lane; k < N; k += WAVE)
@@ -1626,9 +1748,9 @@ __device__ __forceinline__ void st_tracker_quad(const d2d_cfg &c, const d2d_stat
     }
     const int klen = L.klen[k];
     double zx = L.ax[k], zy = L.ay[k];
-    if (s.noise) {
-      zx = zx + c.sigma * s.noise[noise_off + ((size_t)e * N + k) * 2];
-      zy = zy + c.sigma * s.noise[noise_off + ((size_t)e * N + k) * 2 + 1];
+    if (nz) {
+      zx = zx + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2];
+      zy = zy + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2 + 1];
     }
     // ---- predict(), utils.py:225-240: mu <- F mu ; S <- F S ; S <- S F^T ; S += Q (computed by all, selected below) ----
     double m = j < 2 ? mj + 0.1 * mp : mj;
@@ -2021,15 +2143,23 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
     // <= 16 agents on whole grids (SPEC 1): lane = element of a tracker's state, the record read from global memory.  With 17 to 40
     // agents the lane-per-tracker form fetches every filter in ONE round trip where the per-element form needs one per pass of three
     // trackers (config 4's step: 141 us against 160 us per 32768 envs): kept there.
+    // the standard-normal draws of utils.py:605, [B][N][2] from `noise_off` on: the caller's row, or the ones drawn here from the
+    // envs' own streams
+    const double D2D_AS *nz = s.noise;
+    if (c.sigma != 0.0 && !s.noise && s.rng) {  // (never in the specialised kernels: their sigma is the literal 0)
+      st_noise_draw(c, s, e, lane, L);
+      nz = s.rng_draws;
+      noise_off = 0;
+    }
     if (FULL && g.ncap <= 16) {
-      st_tracker_elem(c, s, e, lane, g, L, r, noise_off);
+      st_tracker_elem(c, s, e, lane, g, L, r, nz, noise_off);
     } else {
 #ifdef D2D_TRK_LANE
-      if (g.kf_lds) st_tracker<true>(c, s, e, lane, g, L, r, noise_off);
-      else st_tracker<false>(c, s, e, lane, g, L, r, noise_off);
+      if (g.kf_lds) st_tracker<true>(c, s, e, lane, g, L, r, nz, noise_off);
+      else st_tracker<false>(c, s, e, lane, g, L, r, nz, noise_off);
 #else
-      if (g.kf_lds) st_tracker_quad<true>(c, s, e, lane, g, L, r, noise_off);
-      else st_tracker_quad<false>(c, s, e, lane, g, L, r, noise_off);
+      if (g.kf_lds) st_tracker_quad<true>(c, s, e, lane, g, L, r, nz, noise_off);
+      else st_tracker_quad<false>(c, s, e, lane, g, L, r, nz, noise_off);
 #endif
     }
   }
@@ -2187,8 +2317,17 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_stages
   D2D_STAMP(13);
 }
 
-// reset(): copy of the snapshot over the live state of env e by one wave
-__device__ __forceinline__ void reset_env(const d2d_cfg &c, const d2d_state &s, const d2d_state &init, size_t e, int lane) {
+// reset() re-seeds the stream of the measurement noise, envs/drone_v2.py:259-261: the snapshot's stream over the live one
+__device__ __forceinline__ void rng_reset_env(const d2d_cfg &c, const d2d_state &s, const d2d_state &init, size_t e, int lane) {
+  if (c.sigma != 0.0 && s.rng && init.rng) {
+    for (size_t i = lane; i < D2D_RNG_WORDS; i += WAVE) s.rng[e * D2D_RNG_WORDS + i] = init.rng[e * D2D_RNG_WORDS + i];
+    for (size_t i = lane; i < 2 * (size_t)c.N; i += WAVE) s.rng_draws[e * 2 * c.N + i] = 0.0;
+  }
+}
+
+// reset(): copy of the snapshot over the live state of env e by one wave (`with_rng` false: the caller has run rng_reset_env)
+__device__ __forceinline__ void reset_env(const d2d_cfg &c, const d2d_state &s, const d2d_state &init, size_t e, int lane,
+                                          bool with_rng = true) {
   const size_t N = c.N, WH = grid_bytes(c), LL = (size_t)c.L * c.L;
   for (size_t i = lane; i < D2D_AF * N; i += WAVE) s.agents[e * D2D_AF * N + i] = init.agents[e * D2D_AF * N + i];
   for (size_t i = lane; i < N; i += WAVE) {
@@ -2213,6 +2352,7 @@ __device__ __forceinline__ void reset_env(const d2d_cfg &c, const d2d_state &s, 
       s.dmap[e * WH + i] = init.dmap[e * WH + i];
     }
   }
+  if (with_rng) rng_reset_env(c, s, init, e, lane);
   for (size_t i = lane; i < LL; i += WAVE) s.obs_local[e * LL + i] = 0;
   for (size_t i = lane; i < (size_t)c.T * 2; i += WAVE) s.targets[e * c.T * 2 + i] = init.targets[e * c.T * 2 + i];
   if (lane < D2D_DF) s.drone[e * D2D_DF + lane] = init.drone[e * D2D_DF + lane];
@@ -2238,6 +2378,29 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_reset(d2d_cfg c, d2d_
 __global__ void k_tan(const double *in, double *out, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = d2d_tan(in[i]);
+}
+
+__global__ void k_log(const double *x, double *out, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = d2d_log(x[i]);
+}
+
+// d2d_rng_draw: stream b by the one wave of workgroup b
+__global__ __launch_bounds__(WAVE) void k_rng_draw(uint32_t *rng, const int *m, double *out, int max_m) {
+  const int lane = threadIdx.x;
+  uint32_t *st = rng + (size_t)blockIdx.x * D2D_RNG_WORDS;
+  double *o = out + (size_t)blockIdx.x * max_m * 2;
+  const int mb = __builtin_amdgcn_readfirstlane(min(max(m[blockIdx.x], 0), max_m));
+  int pos = __builtin_amdgcn_readfirstlane((int)st[D2D_RNG_POS]);
+  const bool bad = !rng_pos_ok(pos);
+  int got = 0, regen = 0;
+  if (!bad)
+    got = rng_wave_pairs(st, pos, regen, d2d_rng_regen_cap(mb), mb, lane, [&](int q, double v0, double v1) {
+      o[(size_t)q * 2] = v0;
+      o[(size_t)q * 2 + 1] = v1;
+    });
+  for (int k = got + lane; k < max_m; k += WAVE) o[(size_t)k * 2] = o[(size_t)k * 2 + 1] = k < mb ? __builtin_nan("") : 0.0;
+  if (!bad) rng_wave_store(st, pos, got, regen, lane);
 }
 
 #include "d2d_plugins.h"
@@ -2635,7 +2798,8 @@ int check(const d2d_cfg *c, const d2d_state *s) {
     return fail(-4, "map_scale must be an integer >= 2 (scale 1 never advances a ray, utils.py:621)");
   if (!(c->depth > 0) || !(c->dt > 0)) return fail(-1, "bad depth / dt");
   if (c->kf_enabled && (!s->kf || !s->kf_len)) return fail(-1, "kf_enabled without kf buffers");
-  if (c->sigma != 0.0 && c->kf_enabled && c->N > 0 && !s->noise) return fail(-1, "var_cam != 0 needs the noise input");
+  if (c->sigma != 0.0 && c->kf_enabled && c->N > 0 && !s->noise && !s->rng) return fail(-1, "var_cam != 0 needs the noise input");
+  if (s->rng && !s->rng_draws) return fail(-1, "rng without rng_draws");
   if (!s->agents || !s->agent_unit || !s->dyn_prev || !s->gt || !s->dmap || !s->drone || !s->target || !s->targets ||
       !s->counters || !s->active || !s->hit || !s->newly || !s->flags || !s->obs_local || !s->obs_yaw)
     return fail(-1, "null state pointer");
@@ -2773,6 +2937,9 @@ int gaze_launch(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, const d
   while (wpb > 1 && wb * wpb > LDS_SOFT) wpb >>= 1;
   const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
   const size_t lds = wb * wpb;
+  if (init && c->sigma != 0.0 && s->rng && init->rng)
+    hipLaunchKernelGGL(k_rng_reset_done, dim3((c->B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(WAVE * WAVES_PER_BLOCK), 0,
+                       (hipStream_t)stream, *c, *s, *init);
   if (p->gaze == D2D_GAZE_OWL) {
     hipLaunchKernelGGL(k_gaze_owl, grid, block, 0, (hipStream_t)stream, *c, *s, *p, init ? *init : *s, init ? 1 : (skip_done ? 2 : 0));
   } else {
@@ -3006,6 +3173,25 @@ int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, vo
   if (n == 0) return 0;
   const int bs = 256;
   hipLaunchKernelGGL(k_atan2, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, y, x, out, (long long)n);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
+  return 0;
+}
+
+int d2d_log_array(const double *x, double *out, int64_t n, void *stream) {
+  if (!x || !out || n < 0) return fail(-1, "log_array: bad argument");
+  if (n == 0) return 0;
+  const int bs = 256;
+  hipLaunchKernelGGL(k_log, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, x, out, (long long)n);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
+  return 0;
+}
+
+int d2d_rng_draw(uint32_t *rng, const int32_t *m, double *out, int32_t B, int32_t max_m, void *stream) {
+  if (!rng || !m || !out || B < 0 || max_m < 0) return fail(-1, "rng_draw: bad argument");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(k_rng_draw, dim3((unsigned)B), dim3(WAVE), 0, (hipStream_t)stream, rng, m, out, max_m);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
   return 0;

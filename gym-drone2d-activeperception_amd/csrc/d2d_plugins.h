@@ -1575,7 +1575,7 @@ __device__ D2D_OWL_ATTR void owl_gaze_env(const d2d_cfg &c, const d2d_state &s, 
 // OWL: whether the caller's kernel carries the Owl stage (k_gaze does not: the stage has k_gaze_owl).
 template <bool OWL>
 __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, const d2d_state &init,
-                                         int auto_reset, int e, int lane, char *base, int known_done = -1) {
+                                         int auto_reset, int e, int lane, char *base, int known_done = -1, bool reset_rng = true) {
   // ---- one batch of loads: everything the stage needs that does not hang on another load (the episode flag, the pose, the step
   //      count, the trajectory header, the table heads, the pairwise plan, the candidates' yaw rates) is requested before the first
   //      of them is looked at -- one round trip where the straightforward order makes seven dependent ones ----
@@ -1595,7 +1595,7 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
     tob_l = p.tobs_tab[min(lane, p.tobs_len - 1)];
   }
   if (was_done != 0) {
-    reset_env(c, s, init, (size_t)e, lane);
+    reset_env(c, s, init, (size_t)e, lane, reset_rng);
     plan_reset_env(c, p, (size_t)e, lane);
     wave_sync_global();
     x0 = dr[D2D_D_X]; y0 = dr[D2D_D_Y]; yaw = dr[D2D_D_YAW];  // (the fence above: these are fresh loads)
@@ -2271,14 +2271,24 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
   GZ(7);  // tree + argmax
 }
 
-// mode: 0 plain, 1 reset the envs that are done first, 2 leave the envs that are done untouched
+// The noise stream's part of mode 1's reset, a launch of its own BEFORE k_gaze / k_gaze_owl (gaze_launch): both take two d2d_state
+// by value and are short of scalar registers; the four pointers this needs cost k_gaze_owl a wave per SIMD and 68 B of scratch.
+__global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_rng_reset_done(d2d_cfg c, d2d_state s, d2d_state init) {
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const int e = blockIdx.x * WAVES_PER_BLOCK + wv;
+  if (e >= c.B || s.flags[(size_t)e * 4 + D2D_F_DONE] == 0) return;
+  rng_reset_env(c, s, init, (size_t)e, lane);
+}
+
+// mode: 0 plain, 1 reset the envs that are done first (but for their noise streams: k_rng_reset_done), 2 leave the envs that are
+// done untouched
 __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_gaze(d2d_cfg c, d2d_state s, d2d_plan p, d2d_state init, int mode) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   const int e = blockIdx.x * (int)(blockDim.x / WAVE) + wv;
   if (e >= c.B) return;
   if (mode == 2 && s.flags[(size_t)e * 4 + D2D_F_DONE] != 0) return;
-  gaze_env<false>(c, s, p, init, mode == 1, e, lane, d2d_lds + (size_t)wv * gaze_geom(c, p).wave_bytes);
+  gaze_env<false>(c, s, p, init, mode == 1, e, lane, d2d_lds + (size_t)wv * gaze_geom(c, p).wave_bytes, -1, false);
 }
 
 // k_gaze for D2D_GAZE_OWL (no LDS)
@@ -2288,7 +2298,7 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK) void k_gaze_owl(d2d_cfg c, d
   const int e = blockIdx.x * (int)(blockDim.x / WAVE) + wv;
   if (e >= c.B || p.gaze != D2D_GAZE_OWL) return;
   if (mode == 2 && s.flags[(size_t)e * 4 + D2D_F_DONE] != 0) return;
-  gaze_env<true>(c, s, p, init, mode == 1, e, lane, d2d_lds);
+  gaze_env<true>(c, s, p, init, mode == 1, e, lane, d2d_lds, -1, false);
 }
 
 __global__ void k_pow2(const double *x, double *out, long long n) {

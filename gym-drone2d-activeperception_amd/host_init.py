@@ -156,7 +156,12 @@ def init_world(params):
     counters[A.C_NTGT] = len(targets)
     tracker_radius = np.full(N, float(p.agent_radius), dtype=np.float64)  # utils.py:184
     tracker_radius[:n_rand] = rad[:n_rand]                                # drone_v2.py:46
-    return dict(agents=agents, agent_unit=unit, dyn_prev=dyn_prev, gt=gt,
+    # the global numpy stream as construction leaves it: what utils.py:605 draws the measurement noise from (d2d_state.rng)
+    kind, key, pos, has_gauss, _ = nrs.get_state()
+    assert kind == 'MT19937' and not has_gauss
+    rng = np.zeros(A.RNG_WORDS, dtype=np.uint32)
+    rng[:624], rng[A.RNG_POS] = key, pos
+    return dict(rng=rng, agents=agents, agent_unit=unit, dyn_prev=dyn_prev, gt=gt,
                 dmap=np.zeros((W, H), dtype=np.uint8),                    # utils.py:722 init_num=0
                 drone=drone, target=np.array([dx, dy], dtype=np.float64),  # traj_planner.py:22
                 targets=tl, counters=counters, group=np.array(group, dtype=np.int64),

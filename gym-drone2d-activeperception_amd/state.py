@@ -64,7 +64,18 @@ def _spec(B, N, W, H, L, T, grid_tile=0):
 
 
 WORLD_FIELDS = ('agents', 'agent_unit', 'dyn_prev', 'gt', 'dmap', 'drone', 'target', 'targets', 'counters',
-                'active', 'kf', 'kf_len')
+                'active', 'kf', 'kf_len', 'rng')
+RNG_FIELDS = ('rng', 'rng_draws')      # allocated only when var_cam != 0 (d2d_state.rng: the stream of the measurement noise)
+
+
+def check_rng(rng):
+    """The stream positions the device draws from (include/d2d.h, d2d_state.rng): a multiple of 4, at most 624.  The library cannot
+    look into device memory before a launch, so the host refuses anything else here, before it is uploaded."""
+    pos = np.asarray(rng).reshape(-1, A.RNG_WORDS)[:, A.RNG_POS].astype(np.int64) & 0xffffffff
+    if (pos > 624).any() or (pos % 4 != 0).any():
+        bad = int(pos[(pos > 624) | (pos % 4 != 0)][0])
+        raise ValueError(f'noise stream at position {bad}: the device draws from positions that are multiples of 4 and <= 624 '
+                         '(world construction leaves 200); draw on the host for any other state')
 
 
 class BatchState:
@@ -76,6 +87,10 @@ class BatchState:
         self.t = {}
         for name, (shape, dt) in _spec(cfg.B, cfg.N, cfg.W, cfg.H, cfg.L, cfg.T, cfg.grid_tile).items():
             self.t[name] = torch.zeros(shape, dtype=dt, device=self.device)
+        if cfg.sigma != 0.0:
+            # uint32 words kept as int32 bits (torch's unsigned types are incomplete)
+            self.t['rng'] = torch.zeros((cfg.B, A.RNG_WORDS), dtype=torch.int32, device=self.device)
+            self.t['rng_draws'] = torch.zeros((cfg.B, cfg.N, 2), dtype=torch.float64, device=self.device)
         self.noise = None
         self._dummy = torch.zeros(64, dtype=torch.float64, device=self.device)   # target of empty fields (N == 0)
         self._kf_defaults()
@@ -131,6 +146,17 @@ class BatchState:
                 for c0 in range(0, B, step):                       # (the gather's temporary stays within the same 256 MB)
                     self.t[name][c0:c0 + step] = dst[idx[c0:c0 + step]]
                 del dst
+        if 'rng' in self.t and not all('rng' in w for w in distinct):
+            # worlds that do not say where their stream stands (built by hand, or before host_init handed it over): no device
+            # stream -- the caller supplies the draws (VecDrone2DEnv.set_noise), as a backend without the stage needs them
+            for name in RNG_FIELDS:
+                del self.t[name]
+        if 'rng' in self.t and B:
+            rng = np.stack([np.asarray(w['rng'], dtype=np.uint32) for w in distinct])
+            check_rng(rng)
+            dst = torch.from_numpy(rng.view(np.int32)).to(self.device)
+            self.t['rng'].copy_(dst if idx is None else dst[idx])
+            self.t['rng_draws'].zero_()
         self.t['active'].zero_()
         self._kf_defaults()
 
@@ -147,6 +173,8 @@ class BatchState:
             if name == 'noise':
                 s.noise = self.noise.data_ptr() if self.noise is not None else None
             elif name in ('plan_ok', 'wp_valid', 'wp') and not use_planner_inputs:
+                setattr(s, name, None)
+            elif name in RNG_FIELDS and name not in self.t:
                 setattr(s, name, None)
             else:
                 t = self.t[name]

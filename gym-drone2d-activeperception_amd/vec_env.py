@@ -96,6 +96,12 @@ class VecDrone2DEnv:
         self.init_state = self.state.clone_world()
         self._st = self.state.struct()
         self._init_st = self.init_state.struct()
+        # var_cam != 0: the tracker stage draws the measurement noise from the env's own stream (d2d_state.rng) unless set_noise()
+        # supplies the draws; a backend without that stage sees no stream and refuses the step until it gets them
+        self.device_noise = 'rng' in self.state.t and bool(getattr(backend, 'supports_device_noise', False))
+        if not self.device_noise:
+            for st in (self._st, self._init_st):
+                st.rng = st.rng_draws = None
         self.reward = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)   # drone_v2.py:257
         self.plugins = None
         if device_plugins:
@@ -153,9 +159,9 @@ class VecDrone2DEnv:
         self.state.wp.copy_(torch.as_tensor(wp, dtype=torch.float64).reshape(self.num_envs, 6))
 
     def set_noise(self, noise):
-        """Standard-normal draws for the measurements (utils.py:605); required when var_cam != 0 (the reference takes them
-        from np.random in agent order).  [B, N, 2]: the draws of the next step (every step of a multi-step call would reuse
-        them); [T, B, N, 2]: a run of multi-step calls (rollout() / closed_loop()) draws row after row, step t of the run from
+        """Standard-normal draws for the measurements (utils.py:605) in place of the ones the device draws from the env's own
+        stream; required when var_cam != 0 on a backend without that stage (the reference takes them from np.random in agent
+        order).  [B, N, 2]: the draws of the next step (every step of a multi-step call would reuse them); [T, B, N, 2]: a run of multi-step calls (rollout() / closed_loop()) draws row after row, step t of the run from
         row t % T, as the reference draws fresh normals every step -- also when the run is cut into several calls
         (d2d_cfg.noise_row0 is advanced by the steps of every call; set_noise() starts again at row 0)."""
         n = torch.as_tensor(noise, dtype=torch.float64)

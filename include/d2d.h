@@ -119,6 +119,13 @@ extern "C" {
 /* Kalman record d2d_state.kf: [B][N][D2D_KF] fp64: mu[4], Sigma[16] row-major */
 #define D2D_KF 20
 
+/* one env's random stream d2d_state.rng: [B][D2D_RNG_WORDS] uint32 -- the state of the global numpy stream the reference
+ * seeds with map_id (envs/drone_v2.py:80) and draws the measurement noise from (utils.py:603-605): MT19937 as
+ * np.random.RandomState.get_state() returns it.  Words 0..623: the key; 624: the position (<= 624; 624 = the key is used up);
+ * 625: pairs drawn so far (wraps); 626: regenerations of the key so far; the rest: reserved, zero.  The Gaussian cache of the
+ * stream is always empty between steps (every hit agent takes one randn(2), i.e. both values of a pair) */
+#define D2D_RNG_WORDS 640
+
 /* stage bits for d2d_run_stages */
 #define D2D_ST_FSM 1      /* state machine pre-update, envs/drone_v2.py:153-163      */
 #define D2D_ST_AGENTS 2   /* Agent.step under CVM, utils.py:472-493                  */
@@ -206,13 +213,25 @@ typedef struct d2d_state {
   const uint8_t D2D_AS *plan_ok;  /* [B] planner.plan() result (drone_v2.py:197); NULL under NOMOVE */
   const uint8_t D2D_AS *wp_valid; /* [B] trajectory non-empty at step_pos (utils.py:734); NULL under NOMOVE */
   const double D2D_AS *wp;        /* [B][6] head waypoint: pos(2), vel(2), acc(2) (utils.py:735-738) */
-  const double D2D_AS *noise;     /* [noise_rows][B][N][2] standard normal draws for utils.py:605, or NULL (sigma must be 0) */
+  const double D2D_AS *noise;     /* [noise_rows][B][N][2] standard normal draws for utils.py:605 supplied by the caller, or NULL: the
+                              draws then come from `rng` (sigma must be 0 if that is NULL too) */
   /* ---- outputs of this step (written) ---- */
   uint8_t D2D_AS *hit;        /* [B][N] OR over rays of the per-ray hit lists (utils.py:598-599) */
   int32_t D2D_AS *newly;      /* [B] newly_tracked (utils.py:606-607) */
   uint8_t D2D_AS *flags;      /* [B][4] collision, dead_lock, freezing, done */
   uint8_t D2D_AS *obs_local;  /* [B][L][L] obs['local_map'] (== obs['swep_map'], drone_v2.py:252-253) */
   float D2D_AS *obs_yaw;      /* [B] obs['yaw_angle'] */
+  /* ---- the measurement noise drawn by the library (appended to ABI 8: a binder built against the shorter struct must be rebuilt; liboracle ignores both) ---- */
+  uint32_t D2D_AS *rng;       /* [B][D2D_RNG_WORDS] or NULL.  With sigma != 0 and noise == NULL the tracker stage (D2D_ST_TRACKER) draws
+                          np.random.randn(2) for every agent with `hit` set, in agent order, from the env's stream (utils.py:603-605:
+                          whatever the tracker's `active` or kf_enabled say) and advances it: bit for bit numpy's legacy Gaussian
+                          over MT19937 with the host libm's log.  The position must be a multiple of 4 (world construction leaves
+                          200, and a draw moves it by a multiple of 4); the library cannot look into device memory before a launch,
+                          so a stream with another position, or one above 624, is left untouched and every draw of its env is NaN.
+                          Untouched with sigma == 0 or noise != NULL.  d2d_reset and D2D_DONE_RESET restore it from the snapshot
+                          (reset() re-seeds, envs/drone_v2.py:259-261); FREEZE leaves it as the env ended; CONTINUE lets it run on */
+  double D2D_AS *rng_draws;   /* [B][N][2] (needed with rng): the standard-normal pair each hit agent received in the step just run, 0 for
+                          the agents not hit */
 } d2d_state;
 
 

@@ -23,6 +23,16 @@ int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, vo
  * negative error like every entry point. */
 int d2d_pow2_array(const double *x, double *out, int64_t n, void *stream);
 
+/* Device restatement of the host libm log that numpy's legacy Gaussian calls for the measurement noise (utils.py:605):
+ * out[i] = log(x[i]), bit-for-bit glibc 2.35 x86-64 FMA variant.  Returns 0, or a negative error like every entry point. */
+int d2d_log_array(const double *x, double *out, int64_t n, void *stream);
+
+/* The measurement noise's random stream on its own: draws m[b] pairs (np.random.randn(2) each) from stream b of
+ * rng [B][D2D_RNG_WORDS] into out[b][k][0..1], k < m[b] <= max_m (the rest of out[b] is set to 0), and advances the stream, as the
+ * tracker stage does for the m[b] agents in view (include/d2d.h, d2d_state.rng).  Returns 0, or a negative error like every
+ * entry point. */
+int d2d_rng_draw(uint32_t *rng, const int32_t *m, double *out, int32_t B, int32_t max_m, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
