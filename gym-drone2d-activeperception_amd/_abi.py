@@ -109,3 +109,39 @@ OPTIONAL = ('launch_shape', 'atan2_array', 'pow2_array', 'log_array', 'rng_draw'
 HIP_ONLY_ENTRY_POINTS = ('atan2_array', 'pow2_array', 'log_array', 'rng_draw')
 ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_stages', 'rollout', 'reset',
                 'tan_array', 'gaze_stage', 'plan_stage', 'closed_loop', 'plan_reset', 'sincos_array', 'launch_shape')
+
+
+# ---- include/d2d_worlds.h: the world construction on the device (csrc/worlds/libd2d_worlds.so, its own version) ----
+D2D_WORLDS_VERSION = 1
+WORLDS_ENV_F = 8
+WE_R_LO, WE_R_W, WE_SPEED, WE_TRK_R, WE_X0, WE_Y0, WE_NTGT = range(7)
+WORLDS_MAX_ATTEMPTS = 65536
+WORLD_OK, WORLD_CAP = 0, 1
+WORLD_SPEC_INT_FIELDS = ('version', 'B', 'N', 'n_rand', 'n_cells', 'P', 'T', 'W_px', 'H_px', 'scale', 'W', 'H', 'grid_tile',
+                         'max_attempts')
+WORLD_SPEC_F64_FIELDS = ('start_clear', 'pillar_clear')
+WORLD_SPEC_POINTERS = ('unit', 'cells', 'map_id', 'env_par', 'env_tgt', 'tracker_radius', 'obstacles', 'status')
+
+
+class WorldSpec(C.Structure):
+    """include/d2d_worlds.h `d2d_world_spec`."""
+    _fields_ = [(n, C.c_int32) for n in WORLD_SPEC_INT_FIELDS] + [(n, C.c_double) for n in WORLD_SPEC_F64_FIELDS] + \
+               [(n, C.c_void_p) for n in WORLD_SPEC_POINTERS]
+
+
+def bind_worlds(lib):
+    """argtypes / restypes of include/d2d_worlds.h on a loaded CDLL."""
+    P = C.POINTER
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'build': (C.c_int, [P(WorldSpec), P(State), C.c_void_p]),
+        'launch_shape': (C.c_int, [P(WorldSpec), P(C.c_int32 * 2)]),
+    }
+    out = {}
+    for name, (res, args) in sig.items():
+        fn = getattr(lib, 'd2d_worlds_' + name)
+        fn.restype = res
+        fn.argtypes = args
+        out[name] = fn
+    return out

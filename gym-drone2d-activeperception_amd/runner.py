@@ -73,9 +73,10 @@ class ExperimentBatch:
     step pulls the drone's velocity and yaw, evaluates the policy with the host's libm and uploads the actions -- one
     launch per step instead of one per episode; LookGoal is refused there.  `device_gaze=False` takes that host path for
     LookAhead on any backend (A/B measurements).  `Owl` (yaw_planner.py:151-222) runs as a device gaze stage too and is refused
-    on a backend without it (`supports_device_owl_gaze`)."""
+    on a backend without it (`supports_device_owl_gaze`).  `device_worlds=True`: the seeded worlds are built by the device too
+    (include/d2d_worlds.h) instead of by `workers` host processes."""
 
-    def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_gaze=True):
+    def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_gaze=True, device_worlds=False):
         from .vec_env import VecDrone2DEnv, build_worlds
         from ._lib import HipBackend
         p = with_defaults(params)
@@ -93,7 +94,7 @@ class ExperimentBatch:
         if p.gaze_method == 'NoControl':
             p.drone_view_range = 360                                   # experiment.py:28-29
         self.params = p
-        worlds = build_worlds(p, num_envs, workers=workers)
+        worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
         self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
                                  device_plugins=True, gaze='external' if self._host_lookahead else p.gaze_method)
         self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then

@@ -160,6 +160,30 @@ class BatchState:
         self.t['active'].zero_()
         self._kf_defaults()
 
+    def load_device_worlds(self, dw):
+        """Fill the world fields from a vec_env.DeviceWorlds: a device-to-device copy of its distinct worlds, or a gather through its
+        env -> world index (in slices of <= 256 MB, as load_worlds); nothing passes through the host."""
+        src = dw.state
+        if (src.cfg.N, src.cfg.T, src.cfg.W, src.cfg.H, src.cfg.grid_tile) != (self.cfg.N, self.cfg.T, self.cfg.W, self.cfg.H, self.cfg.grid_tile):
+            raise ValueError('device worlds built for another batch shape (N, T, grid size or grid layout)')
+        if 'rng' in self.t and 'rng' not in src.t:
+            for name in RNG_FIELDS:
+                del self.t[name]
+        B = self.cfg.B
+        for name in WORLD_FIELDS:
+            if name not in self.t:
+                continue
+            s, d = src.t[name].to(self.device), self.t[name]
+            if dw.index is None:
+                d.copy_(s)
+                continue
+            idx = dw.index.to(self.device)
+            step = max(1, (256 << 20) // max(1, s[0].numel() * s.element_size())) if s.shape[0] else B
+            for c0 in range(0, B, step):
+                d[c0:c0 + step] = s[idx[c0:c0 + step]]
+        if 'rng_draws' in self.t:
+            self.t['rng_draws'].zero_()
+
     def clone_world(self):
         """Snapshot of the world fields (reset source)."""
         snap = BatchState.__new__(BatchState)

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .params import Params
-from .vec_env import VecDrone2DEnv, build_worlds, build_worlds_of
+from .vec_env import VecDrone2DEnv, build_worlds, build_worlds_device_of, build_worlds_of
 
 
 def _params(index):
@@ -42,19 +42,32 @@ def survivability_batch(indices, position_step=60, T=24, device='cuda:0', backen
     `timings`: a dict that collects, per call, the seconds spent building the worlds on the host (`build_s`), in the T-step
     rollout on the device with everything resident (`device_s`, synchronised on both sides) and in the host post-processing
     (`post_s`), with `env_steps` and `launches` (bench.py --workload survivability).
-    `worlds`: the seeded worlds of `indices`, one each, when the caller has built them already (survivability_worlds)."""
+    `worlds`: the seeded worlds of `indices`, one each, when the caller has built them already (survivability_worlds); or 'device':
+    every seeded world is built once by the device (vec_env.build_worlds_device_of) and spread over its start cells there."""
     import time
     t_build = time.perf_counter()
     plist = [_params(ix) for ix in indices]
     xs, ys = start_cells(plist[0], position_step)
     cells = [(x, y) for x in xs for y in ys]
     n_steps = len(np.arange(0, T, 0.1))
-    seeded = worlds if worlds is not None else [build_worlds(p, 1)[0] for p in plist]
-    worlds, pins = [], []
-    for w in seeded:
-        worlds += [w] * len(cells)             # every start cell begins from the same seeded world (env.reset())
-        pins += cells
-    env = VecDrone2DEnv(plist[0], len(worlds), device=device, backend=backend, planner='NoMove', worlds=worlds)
+    if isinstance(worlds, str):
+        if worlds != 'device':
+            raise ValueError(f"worlds {worlds!r}: a list of host worlds or 'device'")
+        if backend is None:
+            from ._lib import HipBackend
+            backend = HipBackend(device)
+        pins = cells * len(plist)
+        worlds = build_worlds_device_of(plist, backend=backend).spread(np.repeat(np.arange(len(plist)), len(cells)))
+        worlds_n = len(pins)
+    else:
+        seeded = worlds if worlds is not None else [build_worlds(p, 1)[0] for p in plist]
+        worlds, pins = [], []
+        for w in seeded:
+            worlds += [w] * len(cells)             # every start cell begins from the same seeded world (env.reset())
+            pins += cells
+        worlds_n = len(worlds)
+    env = VecDrone2DEnv(plist[0], worlds_n, device=device, backend=backend, planner='NoMove', worlds=worlds)
+    worlds = range(worlds_n)                       # (only its length is used below)
     actions = torch.zeros((n_steps, len(worlds)), dtype=torch.float64, device=env.device)
     pin = torch.as_tensor(np.asarray(pins, dtype=np.float64), device=env.device)
     ns = streams if streams is not None else (2 if len(worlds) >= 1024 else 1)
@@ -104,15 +117,15 @@ def survivability_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_siz
                         worlds=None):
     """The array the reference saves as collision_states_*.npy (glob_survivability_calculator.py:44-57), in its
     loop order: map_id outermost, then product(agent_num, agent_size, agent_vel).  `worlds`: survivability_worlds() of the same
-    arguments (else the worlds are built here, one after the other)."""
+    arguments (else the worlds are built here, one after the other), or 'device' (built by the device, one launch per agent count)."""
     order = _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds)
-    if worlds is not None and len(worlds) != len(order):
+    if worlds is not None and not isinstance(worlds, str) and len(worlds) != len(order):
         raise ValueError(f'survivability_table: {len(worlds)} worlds for {len(order)} settings')
     result = [None] * len(order)
     for n in agent_numbers:                    # one batch per agent count (a batch shares N)
         sel = [i for i, ix in enumerate(order) if ix['agent_number'] == n]
         got = survivability_batch([order[i] for i in sel], position_step, T, device, backend, timings, streams,
-                                  worlds=None if worlds is None else [worlds[i] for i in sel])
+                                  worlds=worlds if worlds is None or isinstance(worlds, str) else [worlds[i] for i in sel])
         for i, g in zip(sel, got):
             result[i] = g
     return np.array(result)

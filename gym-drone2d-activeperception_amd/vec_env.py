@@ -55,6 +55,158 @@ def build_worlds_of(params_list, workers=0):
     return [_build_world(j) for j in jobs]
 
 
+def world_inputs(params_list, max_attempts=None, map_ids=None):
+    """What the device construction (include/d2d_worlds.h) needs of `params_list`, one world each, as host arrays: the per-batch
+    sizes and tables, the per-env rows, and `group` (the static map's labels, known without building anything).  Everything a
+    batch shares (map, agent_number, pillar_number, static map, drone_radius, number of targets) must agree over the list.
+    `map_ids`: the list is ONE Params and world i is that Params with map_ids[i] (a batch of thousands then costs no Python per env)."""
+    from numpy import cos, pi, sin
+    plist = [with_defaults(p) for p in params_list]
+    if not plist or (map_ids is not None and len(plist) != 1):
+        raise ValueError('no worlds to build' if not plist else 'map_ids goes with exactly one Params')
+    p0 = plist[0]
+    ids = [p.map_id for p in plist] if map_ids is None else list(map_ids)
+
+    def shared(p):
+        return (tuple(p.map_size), p.map_scale, p.agent_number, p.pillar_number, str(p.static_map), p.drone_radius,
+                max(len(p.target_list), 1), p.var_cam != 0)
+    for i, p in enumerate(plist):
+        if shared(p) != shared(p0):
+            raise ValueError(f'world {i}: map, agent_number, pillar_number, static map, drone_radius, number of targets and var_cam '
+                             'are per batch')
+    for i, m in enumerate(ids):
+        if not (isinstance(m, (int, np.integer)) and 0 <= int(m) < 2 ** 32):
+            raise ValueError(f'world {i}: map_id {m!r}: numpy seeds with 0 <= map_id < 2**32 only')
+    W_px, H_px, scale = int(p0.map_size[0]), int(p0.map_size[1]), int(p0.map_scale)
+    if (W_px, H_px, scale) != (p0.map_size[0], p0.map_size[1], p0.map_scale):
+        raise ValueError('device worlds: integer map_size and map_scale')
+    n_rand, P, T = int(p0.agent_number), int(p0.pillar_number), max(len(p0.target_list), 1)
+    if P and (W_px < 100 or H_px < 100):
+        raise ValueError('pillars need a map of at least 100 x 100 px (randint(50, size - 50))')
+    label = host_init.load_static_map(p0.static_map)
+    xs, ys = np.nonzero(label)                       # x-major, as drone_v2.py:55-57 walks the map
+    labs = label[xs, ys].astype(np.int64)
+    if labs.size and (labs.min() < 1 or labs.max() > 99):
+        raise ValueError('static map labels index the 100 drawn velocities: 0 < label < 100')
+    cells = np.stack([xs, ys, labs], axis=1).astype(np.int32).reshape(-1, 3)
+    unit = np.array([[cos(2 * pi * k / n_rand), sin(2 * pi * k / n_rand)] for k in range(n_rand)], dtype=np.float64).reshape(-1, 2)
+    U = len(ids)
+    env_par = np.zeros((len(plist), A.WORLDS_ENV_F), dtype=np.float64)
+    env_tgt = np.zeros((len(plist), T, 2), dtype=np.float64)
+    for i, p in enumerate(plist):
+        a, b = (5, 15) if p.agent_radius == -1 else (p.agent_radius - 2, p.agent_radius + 2)
+        env_par[i, [A.WE_R_LO, A.WE_R_W, A.WE_SPEED, A.WE_TRK_R]] = a, b - a, p.agent_max_speed, p.agent_radius
+        env_par[i, [A.WE_X0, A.WE_Y0, A.WE_NTGT]] = p.init_position[0], p.init_position[1], len(p.target_list)
+        for k, t in enumerate(p.target_list):
+            env_tgt[i, k] = host_init._target_xy(t)
+    if map_ids is not None:
+        env_par, env_tgt = np.repeat(env_par, U, axis=0), np.repeat(env_tgt, U, axis=0)
+    return dict(U=U, N=n_rand + len(cells), n_rand=n_rand, n_cells=len(cells), P=P, T=T, W_px=W_px, H_px=H_px, scale=scale,
+                W=W_px // scale, H=H_px // scale, max_attempts=int(A.WORLDS_MAX_ATTEMPTS if max_attempts is None else max_attempts),
+                start_clear=float(p0.drone_radius + 70), pillar_clear=float(p0.drone_radius + 20), unit=unit, cells=cells,
+                map_id=np.array([int(m) for m in ids], dtype=np.uint64).astype(np.uint32), env_par=env_par, env_tgt=env_tgt,
+                group=np.concatenate([np.zeros(n_rand, dtype=np.int64), labs]), map_ids=[int(m) for m in ids])
+
+
+def world_spec(inp, grid_tile, ptr):
+    """The d2d_world_spec of world_inputs() `inp`; ptr(name) is the address of array `name` where the library will read it."""
+    s = A.WorldSpec()
+    s.version = A.D2D_WORLDS_VERSION
+    s.B = inp['U']
+    for n in ('N', 'n_rand', 'n_cells', 'P', 'T', 'W_px', 'H_px', 'scale', 'W', 'H', 'max_attempts', 'start_clear', 'pillar_clear'):
+        setattr(s, n, inp[n])
+    s.grid_tile = int(grid_tile)
+    for n in A.WORLD_SPEC_POINTERS:
+        setattr(s, n, ptr(n))
+    return s
+
+
+class DeviceWorlds:
+    """Seeded worlds built on the device (HipBackend.build_worlds): `state` holds the `U` distinct ones, `index` ([B] int64 on the
+    device, or None) says which of them env i starts from, so a sweep's start cells share one built world.  `tracker_radius` [U, N],
+    `obstacles` [U, P, 3] and `status` [U] are host copies; `group` [N] comes from the static map."""
+
+    def __init__(self, state, index, inp, tracker_radius, obstacles, status):
+        self.state, self.index = state, index
+        self.N, self.T, self.U = inp['N'], inp['T'], inp['U']
+        self.num_envs = self.U if index is None else int(index.numel())
+        self.tracker_radius, self.obstacles, self.status = tracker_radius, obstacles, status
+        self.group, self.map_ids = inp['group'], inp['map_ids']
+
+    def spread(self, index):
+        """The same built worlds under another env -> world index."""
+        out = DeviceWorlds.__new__(DeviceWorlds)
+        out.__dict__.update(self.__dict__)
+        out.index = torch.as_tensor(index, dtype=torch.int64, device=self.state.device)
+        out.num_envs = int(out.index.numel())
+        return out
+
+
+def _build_into(backend, inp, state, check=True):
+    """Run the device construction of world_inputs() `inp` into BatchState `state` (B = inp['U']); returns the host copies of
+    (tracker_radius, obstacles, status).  Reading them back is the call's only synchronisation."""
+    if not getattr(backend, 'supports_device_worlds', False):
+        raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} has no device world construction: build the '
+                                  'worlds on the host (build_worlds / build_worlds_of)')
+    dev = state.device
+    up = {n: torch.from_numpy(inp[n].view(np.int32) if n == 'map_id' else inp[n]).to(dev) for n in ('unit', 'cells', 'map_id', 'env_par', 'env_tgt')}
+    U, N, P = inp['U'], inp['N'], inp['P']
+    up['tracker_radius'] = torch.zeros((U, N), dtype=torch.float64, device=dev)
+    up['obstacles'] = torch.zeros((U, P, 3), dtype=torch.int32, device=dev)
+    up['status'] = torch.zeros(U, dtype=torch.int32, device=dev)
+    spec = world_spec(inp, state.cfg.grid_tile, lambda n: up[n].data_ptr() if up[n].numel() else state._dummy.data_ptr())
+    backend.build_worlds(spec, state.struct())
+    if 'rng_draws' in state.t:
+        state.t['rng_draws'].zero_()
+    status = up['status'].cpu().numpy()
+    if check and status.any():
+        bad = np.nonzero(status)[0]
+        from ._lib import D2DError
+        raise D2DError(f'device worlds: env {int(bad[0])} (map_id {inp["map_ids"][int(bad[0])]}) could not place its pillars and agents '
+                       f'within max_attempts = {inp["max_attempts"]} ({len(bad)} of {U} envs); the reference would loop for ever')
+    return up['tracker_radius'].cpu(), up['obstacles'].cpu().numpy().astype(np.int64), status
+
+
+def build_worlds_device_of(params_list, device='cuda:0', backend=None, grid_layout=None, max_attempts=None, index=None, check=True,
+                           map_ids=None):
+    """build_worlds_of on the device: one world per Params of the list, built by one launch and left resident (DeviceWorlds).
+    `index`: env -> position in the list, for batches that start many envs from one world.  `check=False` returns instead of raising
+    D2DError when an env hit `max_attempts` (DeviceWorlds.status says which; their fields are 0).  `map_ids`: as in world_inputs."""
+    if backend is None:
+        from ._lib import HipBackend
+        backend = HipBackend(device)
+    inp = world_inputs(params_list, max_attempts, map_ids)
+    p0 = with_defaults(params_list[0])
+    cfg = host_init.derive_cfg(p0, B=inp['U'], N=inp['N'], T=inp['T'], grid_tile=_grid_tile(p0, backend, grid_layout))
+    state = BatchState(cfg, torch.device(backend.device))
+    tr, obs, status = _build_into(backend, inp, state, check)
+    idx = None if index is None else torch.as_tensor(index, dtype=torch.int64, device=state.device)
+    return DeviceWorlds(state, idx, inp, tr, obs, status)
+
+
+def build_worlds_device(params, num_envs, env_offset=0, device='cuda:0', backend=None, grid_layout=None, max_attempts=None, check=True):
+    """build_worlds on the device: env i is the reference world for map_id + env_offset + i."""
+    return build_worlds_device_of([params], device, backend, grid_layout, max_attempts, check=check,
+                                  map_ids=_seeded(params, num_envs, env_offset))
+
+
+def _seeded(params, num_envs, env_offset):
+    m0 = with_defaults(params).map_id + env_offset
+    return [m0 + i for i in range(num_envs)]
+
+
+def _grid_tile(params, backend, grid_layout):
+    """d2d_cfg.grid_tile of `grid_layout` ('rowmajor' = the reference's [W][H]; 'tiled' = 16 x 16-cell tiles).  Default: tiled on the
+    HIP backend for grids above 256 x 256 cells (BASELINE config 5: a 3 x 3 block or a 23-byte window row of a 640-cell row-major
+    grid costs a cache line each), row-major otherwise; `state.logical()` / the facade proxies always speak [W][H]."""
+    W, H = params.map_size[0] // params.map_scale, params.map_size[1] // params.map_scale
+    if grid_layout is None:
+        grid_layout = 'tiled' if (W * H > 256 * 256 and getattr(backend, 'supports_tiled_grids', False)) else 'rowmajor'
+    if grid_layout not in ('rowmajor', 'tiled'):
+        raise ValueError(f'grid_layout {grid_layout!r}: rowmajor or tiled')
+    return 16 if grid_layout == 'tiled' else 0
+
+
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
                  kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None):
@@ -68,31 +220,43 @@ class VecDrone2DEnv:
             backend = HipBackend(device)
         self.backend = backend
         self.device = torch.device(backend.device)
-        if worlds is None:
-            worlds = build_worlds(self.params, self.num_envs, self.env_offset, workers=0)
-        N = worlds[0]['N'] if worlds else 0
-        T = worlds[0]['T'] if worlds else 1
-        if any(w['N'] != N for w in worlds):
-            raise ValueError('all envs of a batch must have the same number of agents')
-        # device layout of the two grids (include/d2d.h d2d_cfg.grid_tile): 'rowmajor' = the reference's [W][H]; 'tiled' = 16 x 16-cell
-        # tiles.  Default: tiled on the HIP backend for grids above 256 x 256 cells (BASELINE config 5: a 3 x 3 block or a 23-byte
-        # window row of a 640-cell row-major grid costs a cache line each), row-major otherwise; `state.logical()` / the facade
-        # proxies always speak [W][H].
-        W, H = self.params.map_size[0] // self.params.map_scale, self.params.map_size[1] // self.params.map_scale
-        if grid_layout is None:
-            grid_layout = 'tiled' if (W * H > 256 * 256 and getattr(backend, 'supports_tiled_grids', False)) else 'rowmajor'
-        if grid_layout not in ('rowmajor', 'tiled'):
-            raise ValueError(f'grid_layout {grid_layout!r}: rowmajor or tiled')
-        self.cfg = host_init.derive_cfg(self.params, B=self.num_envs, N=N, T=T, planner_mode=self.planner_mode,
-                                        kf_enabled=kf_enabled, grid_tile=16 if grid_layout == 'tiled' else 0)
-        self.state = BatchState(self.cfg, self.device)
-        self.state.load_worlds(worlds)
-        if worlds:
-            from .state import distinct_worlds
-            distinct, index = distinct_worlds(worlds)
-            self.tracker_radius = torch.from_numpy(np.stack([w['tracker_radius'] for w in distinct]))[torch.as_tensor(index)]
+        # worlds='device' / a DeviceWorlds: the seeded worlds are built by the device (include/d2d_worlds.h) and never exist on the host;
+        # N and T follow from the parameters and the static map
+        dw = worlds if isinstance(worlds, DeviceWorlds) else None
+        on_device = dw is not None or (isinstance(worlds, str) and worlds == 'device')
+        if isinstance(worlds, str) and not on_device:
+            raise ValueError(f"worlds {worlds!r}: a list of host worlds, a DeviceWorlds or 'device'")
+        if on_device and not getattr(backend, 'supports_device_worlds', False):
+            raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} has no device world construction: build '
+                                      'the worlds on the host (build_worlds / build_worlds_of)')
+        if on_device:
+            inp = None if dw is not None else world_inputs([self.params], map_ids=_seeded(self.params, self.num_envs, self.env_offset))
+            N, T = (dw.N, dw.T) if dw is not None else (inp['N'], inp['T'])
+            if dw is not None and dw.num_envs != self.num_envs:
+                raise ValueError(f'{dw.num_envs} device worlds for {self.num_envs} envs')
         else:
-            self.tracker_radius = None
+            if worlds is None:
+                worlds = build_worlds(self.params, self.num_envs, self.env_offset, workers=0)
+            N = worlds[0]['N'] if worlds else 0
+            T = worlds[0]['T'] if worlds else 1
+            if any(w['N'] != N for w in worlds):
+                raise ValueError('all envs of a batch must have the same number of agents')
+        self.cfg = host_init.derive_cfg(self.params, B=self.num_envs, N=N, T=T, planner_mode=self.planner_mode,
+                                        kf_enabled=kf_enabled, grid_tile=_grid_tile(self.params, backend, grid_layout))
+        self.state = BatchState(self.cfg, self.device)
+        if dw is not None:
+            self.state.load_device_worlds(dw)
+            self.tracker_radius = dw.tracker_radius if dw.index is None else dw.tracker_radius[dw.index.cpu()]
+        elif on_device:
+            self.tracker_radius = _build_into(backend, inp, self.state)[0] if self.num_envs else None
+        else:
+            self.state.load_worlds(worlds)
+            if worlds:
+                from .state import distinct_worlds
+                distinct, index = distinct_worlds(worlds)
+                self.tracker_radius = torch.from_numpy(np.stack([w['tracker_radius'] for w in distinct]))[torch.as_tensor(index)]
+            else:
+                self.tracker_radius = None
         self.init_state = self.state.clone_world()
         self._st = self.state.struct()
         self._init_st = self.init_state.struct()
