@@ -56,10 +56,17 @@ def expected(pkg, name, plist, grid_tile=0):
     key = (name, grid_tile)
     if key in _expected_cache:
         return _expected_cache[key]
-    from drone2d_amd import host_init, state
+    from drone2d_amd import host_init
     from drone2d_amd.params import with_defaults
+    out = stack_worlds(pkg, [host_init.init_world(with_defaults(p)) for p in plist], grid_tile)
+    _expected_cache[key] = out
+    return out
+
+
+def stack_worlds(pkg, ws, grid_tile=0):
+    """host_init.init_world dicts `ws`, stacked the way the batch stores them, read-only"""
+    from drone2d_amd import state
     A = pkg._abi
-    ws = [host_init.init_world(with_defaults(p)) for p in plist]
     out = {}
     for f in ('agents', 'agent_unit', 'dyn_prev', 'gt', 'dmap', 'drone', 'target', 'targets', 'counters', 'tracker_radius',
               'obstacles', 'rng'):
@@ -78,7 +85,6 @@ def expected(pkg, name, plist, grid_tile=0):
     out['group'] = ws[0]['group']
     for a in out.values():
         a.setflags(write=False)
-    _expected_cache[key] = out
     return out
 
 
