@@ -13,6 +13,7 @@ Layout
   gaze.py        --gaze_method plugin surface (yaw_planner.py): Oxford = the device stage, NoControl, Rotating
   device_plugins.py  host tables + per-env state of the device planner / gaze stages (d2d_plan)
   sweeps.py      survivability sweeps (glob_survivability_calculator.py) on d2d_rollout
+  metrics.py     velocity-obstacle feasibility and density metrics (vo_calculator.py, density_calculator.py) on include/d2d_metrics.h
   runner.py      Experiment: one episode -> the reference's CSV row (experiment.py)
   dist.py        env sharding across GPUs, RCCL gather of episode statistics
 

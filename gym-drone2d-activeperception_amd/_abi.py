@@ -145,3 +145,27 @@ def bind_worlds(lib):
         fn.argtypes = args
         out[name] = fn
     return out
+
+
+# ---- include/d2d_metrics.h: the difficulty metrics on the device (csrc/metrics/libd2d_metrics.so, its own version) ----
+D2D_METRICS_VERSION = 1
+VO_MAX_B, VO_MAX_P, VO_MAX_ELEMS = 65535, 64 * 65535, 0x7fffffff
+
+
+def bind_metrics(lib):
+    """argtypes / restypes of include/d2d_metrics.h on a loaded CDLL."""
+    V, I = C.c_void_p, C.c_int32
+    sig = {
+        'd2d_metrics_version': (C.c_int, []),
+        'd2d_metrics_last_error': (C.c_char_p, []),
+        'd2d_vo_geometry': (C.c_int, [V, V, C.c_double, I, I, I, V, V, V, V]),
+        'd2d_vo_cones': (C.c_int, [V, V, V, I, I, I, V, V]),
+        'd2d_vo_count': (C.c_int, [V, V, V, V, I, I, I, I, V, V]),
+    }
+    out = {}
+    for name, (res, args) in sig.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+        out[name.replace('d2d_metrics_', '').replace('d2d_', '')] = fn
+    return out

@@ -8,6 +8,7 @@ from . import _abi as A
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('D2D_LIB') or os.path.join(_HERE, 'csrc', 'libd2d_hip.so')   # D2D_LIB: A/B builds
 WORLDS_LIB_PATH = os.path.join(_HERE, 'csrc', 'worlds', 'libd2d_worlds.so')             # include/d2d_worlds.h
+METRICS_LIB_PATH = os.path.join(_HERE, 'csrc', 'metrics', 'libd2d_metrics.so')          # include/d2d_metrics.h
 
 
 class D2DError(RuntimeError):
@@ -55,6 +56,20 @@ def load_worlds_library(path=WORLDS_LIB_PATH):
     return lib, fn
 
 
+def load_metrics_library(path=METRICS_LIB_PATH):
+    """The difficulty metrics' own library (include/d2d_metrics.h), after torch like the other ones."""
+    import torch  # noqa: F401
+    if not os.path.isfile(path):
+        raise D2DError(f'{path} not found: build it with gym-drone2d-activeperception_amd/csrc/metrics/build.sh '
+                       '(or __graft_entry__.build()); there is no CPU fallback')
+    lib = C.CDLL(path)
+    fn = A.bind_metrics(lib)
+    v = fn['version']()
+    if v != A.D2D_METRICS_VERSION:
+        raise D2DError(f'libd2d_metrics.so version {v} != expected {A.D2D_METRICS_VERSION}: rebuild')
+    return lib, fn
+
+
 class HipBackend:
     """Thin call surface over the C ABI; launches go to torch's current HIP stream of `device`."""
     name = 'hip'
@@ -63,6 +78,7 @@ class HipBackend:
     supports_device_owl_gaze = True       # d2d_plan.gaze = Owl
     supports_device_noise = True          # d2d_state.rng: the tracker stage draws the measurement noise itself (var_cam != 0)
     supports_device_worlds = True         # include/d2d_worlds.h: the seeded worlds are built on the device
+    supports_vo_metric = True             # include/d2d_metrics.h: the velocity-obstacle feasibility metric (metrics.py)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -72,6 +88,7 @@ class HipBackend:
         self.device = torch.device(device)
         self.lib, self.fn = load_library()
         self.wlib, self.wfn = load_worlds_library()
+        self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -137,6 +154,30 @@ class HipBackend:
         rc = self.wfn['build'](C.byref(spec), C.byref(st), self._stream())
         if rc != 0:
             raise D2DError(f'd2d_worlds error {rc}: {self.wfn["last_error"]().decode()}')
+
+    def _metrics(self, name, *args):
+        if self.mfn is None:
+            self.mlib, self.mfn = load_metrics_library()
+        rc = self.mfn[name](*args, self._stream())
+        if rc != 0:
+            raise D2DError(f'd2d_metrics error {rc}: {self.mfn["last_error"]().decode()}')
+
+    def vo_geometry(self, agents, pos, rA, arg, theta_ba, collided):
+        """d2d_vo_geometry: agents [B, 6, N], pos [P, 2] -> arg, theta_ba [B, P, N] float64, collided [B, P] uint8"""
+        B, _, N = agents.shape
+        self._metrics('vo_geometry', agents.data_ptr(), pos.data_ptr(), float(rA), B, N, pos.shape[0], arg.data_ptr(),
+                      theta_ba.data_ptr(), collided.data_ptr())
+
+    def vo_cones(self, theta_ba, half, collided, cone):
+        """d2d_vo_cones: theta_ba, half [B, P, N], collided [B, P] -> cone [B, P, N, 2] (theta_right, theta_left)"""
+        B, P, N = theta_ba.shape
+        self._metrics('vo_cones', theta_ba.data_ptr(), half.data_ptr(), collided.data_ptr(), B, N, P, cone.data_ptr())
+
+    def vo_count(self, agents, cand, cone, collided, count):
+        """d2d_vo_count: agents [B, 6, N], cand [C, 2], cone, collided -> count [B, P] int32 (-1: collided position)"""
+        B, P, N, _ = cone.shape
+        self._metrics('vo_count', agents.data_ptr(), cand.data_ptr(), cone.data_ptr(), collided.data_ptr(), B, N, P, cand.shape[0],
+                      count.data_ptr())
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))
