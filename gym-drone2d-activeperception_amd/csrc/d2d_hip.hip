@@ -952,9 +952,7 @@ __device__ __forceinline__ void ray_march(const GX &gx, const d2d_cfg &c, const 
         dm[gi] = v;
         if (patch) dmt[gi] = v;  // the copy the observation crop is cut from
       } else {
-#ifndef D2D_ABL_NOSTORE
         dm[(unsigned int)gx(ci, cj)] = v;
-#endif
         const unsigned int pr = (unsigned int)(ci - ct.i0), pq = (unsigned int)(cj - ct.j0);  // observation tile in step
         if (patch && pr < (unsigned int)ct.rows && pq < (unsigned int)ct.cols) dmt[pr * ct.cols + pq] = v;
       }
@@ -1418,154 +1416,12 @@ __device__ __forceinline__ void st_noise_draw(const d2d_cfg &c, const d2d_state 
   wave_sync_global();  // the trackers read the draws of other lanes
 }
 
-// ---- Kalman trackers, utils.py:172-275; lane = tracker slot ----
+// ---- Kalman trackers, utils.py:172-275 ----
 // F = [[1,0,.1,0],[0,1,0,.1],[0,0,1,0],[0,0,0,1]] and H = [I2 0] are constant, so the dense products
 // of the reference collapse: multiplying by an exact 0 or 1 and adding an exact 0 do not round, hence the
 // sparse expressions below give the same values as the oracle's dense loops (tests compare bit for bit).
-template <bool KF_LDS>
-__device__ __forceinline__ void st_tracker(const d2d_cfg &c, const d2d_state &s, int e, int lane, const Geom &g,
-                                           const LdsView &L, EnvRegs &r, const double D2D_AS *nz, size_t noise_off) {
-  const int N = c.N;
-  int arch_n = 0, arch_ts = 0;
-  // More than 128 agents: the few trackers that have anything to do (active, or hit this step) are spread over all lane passes,
-  // and every pass with one of them pays for the whole filter.  Their indices are gathered first -- into the ray candidates'
-  // planes, which nothing reads after the raycast (room for 16 * ccap indices) -- and the filter runs over that list: one pass
-  // instead of three at BASELINE config 3's 172 agents.
-  short *need_list = (short *)L.cx;
-  const bool gather = c.kf_enabled && N > 2 * WAVE && N <= 16 * g.ccap;  // three passes or more (two: the gathering costs what it saves)
-  int nwork = N;
-  if (gather) {
-    nwork = 0;
-    for (int k0 = 0; k0 < N; k0 += WAVE) {
-      const int k = k0 + lane;
-      const bool need = k < N && (L.act[k] != 0 || L.hit[k] != 0);
-      const unsigned long long m = __ballot(need);
-      if (need) need_list[nwork + __popcll(m & ((1ull << lane) - 1ull))] = (short)k;
-      nwork += __popcll(m);
-    }
-    wave_sync_lds();
-  }
-  for (int q0 = 0; q0 < nwork; q0 += WAVE) {
-    const int q = q0 + lane;
-    const int k = gather ? (q < nwork ? (int)need_list[q] : N) : q;
-    if (k < N) {
-      const bool has_z = L.hit[k] != 0;
-      unsigned char act = L.act[k];
-      if (!c.kf_enabled) {
-        if (has_z && !act) s.active[(size_t)e * N + k] = 1;
-      } else if (act || has_z) {
-        double *__restrict__ gk = s.kf + ((size_t)e * N + k) * D2D_KF;
-        int len = 1;
-        double zx = L.ax[k], zy = L.ay[k];
-        if (nz) {
-          zx = zx + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2];
-          zy = zy + c.sigma * nz[noise_off + ((size_t)e * N + k) * 2 + 1];
-        }
-        double m0, m1, m2, m3;
-        double S[16];
-        if (act) {
-          len = L.klen[k];
-          if (KF_LDS) {
-            const double *lk = L.kf + k * D2D_KF;
-            m0 = lk[0]; m1 = lk[1]; m2 = lk[2]; m3 = lk[3];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) S[i] = lk[4 + i];
-          } else {
-            m0 = gk[0]; m1 = gk[1]; m2 = gk[2]; m3 = gk[3];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) S[i] = gk[4 + i];
-          }
-          // predict(), utils.py:225-240, in place (each line only reads entries not yet overwritten):
-          // mu <- F mu ; S <- F S ; S <- S F^T ; S += Q
-          const double qn = (c.sigma != 0.0) ? 0.1 : 0.001;
-          m0 = m0 + 0.1 * m2;
-          m1 = m1 + 0.1 * m3;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            S[j] = S[j] + 0.1 * S[8 + j];
-            S[4 + j] = S[4 + j] + 0.1 * S[12 + j];
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            S[4 * i + 0] = S[4 * i + 0] + S[4 * i + 2] * 0.1;
-            S[4 * i + 1] = S[4 * i + 1] + S[4 * i + 3] * 0.1;
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i) S[5 * i] += qn;
-          len += 1;
-          if (S[0] >= 150.0 || !(c.kf_lo_x < m0 && m0 < c.kf_hi_x) || !(c.kf_lo_y < m1 && m1 < c.kf_hi_y)) {
-            arch_n += 1;  // archived copy -> tracker_buffer
-            arch_ts += len;
-            m0 = m1 = m2 = m3 = 0.0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) S[i] = 0.0;
-            S[0] = 1.0;
-            S[5] = 1.0;
-            S[10] = 10.0;
-            S[15] = 10.0;
-            len = 1;
-            act = 0;
-          }
-          if (has_z) {  // update, utils.py:249-260 (also runs on the freshly reset filter)
-            const double a = c.sigma + S[0], b = S[1], cc = S[4], d = c.sigma + S[5];
-            const double det = a * d - b * cc;
-            const double idet = 1.0 / det;  // inv(S) through one reciprocal (same in oracle/d2d_oracle.c)
-            const double i00 = d * idet, i01 = -b * idet, i10 = -cc * idet, i11 = a * idet;
-            double K0[4], K1[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              K0[i] = S[4 * i] * i00 + S[4 * i + 1] * i10;
-              K1[i] = S[4 * i] * i01 + S[4 * i + 1] * i11;
-            }
-            const double rx = zx - m0, ry = zy - m1;
-            const double e00 = 1.0 - K0[0], e01 = 0.0 - K1[0], e10 = 0.0 - K0[1], e11 = 1.0 - K1[1];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {  // S <- (I - K H) S, rows 2,3 first (they read rows 0,1), then 0,1
-              const double s0 = S[j], s1 = S[4 + j];
-              S[8 + j] = ((0.0 - K0[2]) * s0 + (0.0 - K1[2]) * s1) + S[8 + j];
-              S[12 + j] = ((0.0 - K0[3]) * s0 + (0.0 - K1[3]) * s1) + S[12 + j];
-              S[j] = e00 * s0 + e01 * s1;
-              S[4 + j] = e10 * s0 + e11 * s1;
-            }
-            m0 = m0 + (K0[0] * rx + K1[0] * ry);
-            m1 = m1 + (K0[1] * rx + K1[1] * ry);
-            m2 = m2 + (K0[2] * rx + K1[2] * ry);
-            m3 = m3 + (K0[3] * rx + K1[3] * ry);
-          }
-        } else {  // first sighting, utils.py:263-273
-          m0 = zx;
-          m1 = zy;
-          m2 = 0.0;
-          m3 = 0.0;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) S[i] = 0.0;
-          S[0] = 1.0;
-          S[5] = 1.0;
-          S[10] = 10.0;
-          S[15] = 10.0;
-          len = 1;
-          act = 1;
-        }
-        gk[0] = m0;
-        gk[1] = m1;
-        gk[2] = m2;
-        gk[3] = m3;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) gk[4 + i] = S[i];
-        s.kf_len[(size_t)e * N + k] = len;
-        s.active[(size_t)e * N + k] = act;
-        L.act[k] = act;
-        L.klen[k] = len;
-      }
-    }
-  }
-  if (c.kf_enabled) {
-    r.bufn += wave_sum(arch_n);
-    r.bufts += wave_sum(arch_ts);
-  }
-}
-
-// The same stage with lane = ONE ELEMENT of one tracker's state (mu[4], Sigma[16]: 20 lanes per tracker, three trackers per pass):
+//
+// The stage with lane = ONE ELEMENT of one tracker's state (mu[4], Sigma[16]: 20 lanes per tracker, three trackers per pass):
 // the kernel for few agents (SPEC 1), where one to three trackers have anything to do in a step.  With a lane per tracker the
 // stage keeps a whole filter in registers -- 16 + 8 + 8 doubles: the register peak of the kernel (111 VGPRs with it, 82 without)
 // -- and issues a filter's ~170 instructions for one active lane.  Here every lane forms its own element, in two steps through
@@ -2044,9 +1900,6 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
   int ncand = 0;
   if (do_ray) {
     ncand = ray_cull<CONE>(c, lane, L, x0, y0, yaw0, g.ccap);
-#ifdef D2D_ABL_NOCAND
-    ncand = 0;
-#endif
   }
   wave_sync_lds();
   D2D_STAMP(4);
@@ -2102,9 +1955,7 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
           const unsigned char w0 = ((const unsigned char *)L.gtw)[g0];
           const unsigned char v0 = (w0 == D2D_OCCUPIED) ? (unsigned char)D2D_OCCUPIED : (unsigned char)D2D_UNOCCUPIED;
           if (lane == 0) {
-#ifndef D2D_ABL_NOSTORE
             dm[gx(ocx, ocy)] = v0;
-#endif
             if constexpr (FULL) {
               if (do_obs) ((unsigned char *)L.dmt)[g0] = v0;
             } else {
@@ -2138,11 +1989,9 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
     landed();
   }
   D2D_STAMP(7);
-#ifndef D2D_ABL_NOTRK
   if (do_trk) {  // two instantiations: a run-time choice between an LDS and a global pointer would become flat loads
-    // <= 16 agents on whole grids (SPEC 1): lane = element of a tracker's state, the record read from global memory.  With 17 to 40
-    // agents the lane-per-tracker form fetches every filter in ONE round trip where the per-element form needs one per pass of three
-    // trackers (config 4's step: 141 us against 160 us per 32768 envs): kept there.
+    // <= 16 agents on whole grids (SPEC 1): lane = element of a tracker's state, the record read from global memory.  With more
+    // agents a pass of the per-element form holds three trackers only: four lanes per tracker there (st_tracker_quad).
     // the standard-normal draws of utils.py:605, [B][N][2] from `noise_off` on: the caller's row, or the ones drawn here from the
     // envs' own streams
     const double D2D_AS *nz = s.noise;
@@ -2154,18 +2003,11 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
     if (FULL && g.ncap <= 16) {
       st_tracker_elem(c, s, e, lane, g, L, r, nz, noise_off);
     } else {
-#ifdef D2D_TRK_LANE
-      if (g.kf_lds) st_tracker<true>(c, s, e, lane, g, L, r, nz, noise_off);
-      else st_tracker<false>(c, s, e, lane, g, L, r, nz, noise_off);
-#else
       if (g.kf_lds) st_tracker_quad<true>(c, s, e, lane, g, L, r, nz, noise_off);
       else st_tracker_quad<false>(c, s, e, lane, g, L, r, nz, noise_off);
-#endif
     }
   }
-#endif
   D2D_STAMP(8);
-#ifndef D2D_ABL_NODYN
   if (do_dyn) {
     if constexpr (FULL) {
       dyn_full(c, s, e, lane, L, gt);
@@ -2193,20 +2035,15 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
       }
     }
   }
-#endif
   D2D_STAMP(9);
-#ifndef D2D_ABL_NOCOL
   if (do_col) st_collide(c, s, e, lane, L, probe_wall, r);
-#endif
   D2D_STAMP(10);
   D2D_STAMP(11);
-#ifndef D2D_ABL_NOOBS
   if (do_obs) {
     wave_sync_lds();
     if constexpr (FULL) obs_full(c, s, e, lane, L, ncx_d, ncy_d, r);
     else st_obs(c, s, e, lane, L, r);
   }
-#endif
   D2D_STAMP(12);
 }
 
@@ -2301,10 +2138,6 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_stages
   if (d2d_stamp_buf && lane == 0) d2d_stamp_buf[(size_t)e * 16 + 0] = __builtin_amdgcn_s_memtime();
 #endif
   load_regs(s, e, r);
-#ifdef D2D_NO_PIN
-  pin = nullptr;
-  coll_out = nullptr;
-#endif
   if (pin) {  // d2d_rollout: env.drone.x = x; env.drone.y = y before the step
     r.x = pin[(size_t)e * 2];
     r.y = pin[(size_t)e * 2 + 1];
@@ -2420,9 +2253,9 @@ __global__ void k_atan2(const double *y, const double *x, double *out, long long
 // takes the launch-per-stage path.
 // ------------------------------------------------------------------------------------------------
 // The launch arguments (four structs of pointers) are parked once in device memory (d2d_plan.launch_args) and every
-// phase is a NON-INLINED function that reads what it needs through scalar loads: inlined into one loop body the
-// by-value arguments all stay live across the loop (474 SGPR + 419 VGPR spills, measured); as calls each phase
-// gets the register allocation it has as a kernel of its own.
+// phase reads what it needs through scalar loads: as by-value kernel arguments they all stay live across the step loop
+// (474 SGPR + 419 VGPR spills, measured).  The phases are inlined into the kernel; each launders what it starts from
+// (phase_enter), and so keeps the live ranges it would have as a function of its own.
 struct ClosedArgs {
   d2d_cfg c;
   d2d_state s;
@@ -2463,20 +2296,19 @@ typedef const ClosedArgs *ArgsPtr;  // the host pass only parses the device func
 #endif
 
 // What a phase starts from: the bundle's address, the env index, the LDS offset of the wave -- wave-uniform by construction, said so
-// with readfirstlane -- and the lane index.  A phase that is INLINED into the persistent kernel (D2D_PH_INLINE / the search) launders
+// with readfirstlane -- and the lane index.  Every phase is INLINED into the persistent kernel and launders
 // them through an empty asm: nothing it computes is then loop-invariant in the caller's step loop (hoisted out of the loop, such
 // values stay live across the other phases and spill), and every phase keeps the live ranges it has as a function of its own.
 struct PhaseIn {
   ArgsPtr a;
   int e, off, lane;
 };
-template <bool LAUNDER>
 __device__ __forceinline__ PhaseIn phase_enter(const ClosedArgs *ap, int e_, int lds_off_) {
   const unsigned long long v = (unsigned long long)ap;
   unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)v), hi = __builtin_amdgcn_readfirstlane((unsigned int)(v >> 32));
   int e = __builtin_amdgcn_readfirstlane(e_), off = __builtin_amdgcn_readfirstlane(lds_off_);
   int lane = threadIdx.x & (WAVE - 1);
-  if constexpr (LAUNDER) asm volatile("; phase" : "+s"(lo), "+s"(hi), "+s"(e), "+s"(off), "+v"(lane));
+  asm volatile("; phase" : "+s"(lo), "+s"(hi), "+s"(e), "+s"(off), "+v"(lane));
   PhaseIn in;
   in.a = (ArgsPtr)(((unsigned long long)hi << 32) | lo);
   in.e = e;
@@ -2490,24 +2322,13 @@ __device__ __forceinline__ PhaseIn phase_enter(const ClosedArgs *ap, int e_, int
 // building WITHOUT MachineLICM (csrc/build.sh: -mllvm -disable-machine-licm) -- that pass hoists the 64-bit constants of every phase
 // (polynomial coefficients of tan / sin / cos, thresholds) to the kernel's entry, where they are live across the whole step loop;
 // a 64-bit literal is two moves and not rematerialisable, so the allocator SPILLS constants (18 at entry, ~130 reloads inside the
-// loop, and scalar ones into VGPR lanes).  Without the pass the inlined kernel has no scratch at all.  -DD2D_PH_CALLS builds the
-// called form (the search stays inlined), e.g. for A/B runs.
-#ifndef D2D_PH_CALLS
-#define D2D_PH_INLINE 1
-#endif
-#ifdef D2D_PH_INLINE
-#define D2D_PH_ATTR __forceinline__
-constexpr bool kPhaseLaunder = true;
-#else
-#define D2D_PH_ATTR __attribute__((noinline))
-constexpr bool kPhaseLaunder = false;
-#endif
+// loop, and scalar ones into VGPR lanes).  Without the pass the inlined kernel has no scratch at all.
 
 // The planner stage as two calls: the part every step runs (small: few registers to save), and the search, called
 // only when the trajectory is empty (a few percent of the steps).
 template <int SPEC>
-__device__ D2D_PH_ATTR int ph_plan_quick(const ClosedArgs *ap, int e_, int lds_off_) {
-  const PhaseIn in_ = phase_enter<kPhaseLaunder>(ap, e_, lds_off_);
+__device__ __forceinline__ int ph_plan_quick(const ClosedArgs *ap, int e_, int lds_off_) {
+  const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
   const int e = in_.e, lane = in_.lane;
   char *base = d2d_lds + in_.off;
@@ -2529,20 +2350,10 @@ __device__ D2D_PH_ATTR int ph_plan_quick(const ClosedArgs *ap, int e_, int lds_o
 // bundle's address, the env index, the LDS offset, the lane index) is laundered through an empty asm at the call site, so that no
 // value of the search is loop-invariant in the caller's step loop: hoisted out of it, such values stay live across the other
 // phases' calls and spill.  Same-call A/B against the called form: config 2 +3 % (600 / 300 and the driver's 20-step window),
-// config 3 +4 %, config 4 +2.4 %.  -DD2D_SEARCH_CALL builds the called form.
-#ifndef D2D_SEARCH_CALL
-#define D2D_SEARCH_INLINE 1
-#define D2D_SEARCH_ATTR __forceinline__
-#else
-#define D2D_SEARCH_ATTR __attribute__((noinline))
-#endif
+// config 3 +4 %, config 4 +2.4 %.
 template <int SPEC>
-__device__ D2D_SEARCH_ATTR void ph_plan_search(const ClosedArgs *ap, int e_, int lds_off_) {
-#ifdef D2D_SEARCH_INLINE
-  const PhaseIn in_ = phase_enter<true>(ap, e_, lds_off_);
-#else
-  const PhaseIn in_ = phase_enter<false>(ap, e_, lds_off_);
-#endif
+__device__ __forceinline__ void ph_plan_search(const ClosedArgs *ap, int e_, int lds_off_) {
+  const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
   const int e = in_.e, lane = in_.lane;
   char *base = d2d_lds + in_.off;
@@ -2563,8 +2374,8 @@ __device__ D2D_SEARCH_ATTR void ph_plan_search(const ClosedArgs *ap, int e_, int
 // `walls_ok`: the env's "every remaining waypoint passed the wall test and only rays have written the map since" flag
 // (plan_env_quick), carried by the caller across the steps of a launch.
 template <int SPEC>
-__device__ D2D_PH_ATTR int ph_plan_act(const ClosedArgs *ap, int e_, int lds_off_, int &walls_ok) {
-  const PhaseIn in_ = phase_enter<kPhaseLaunder>(ap, e_, lds_off_);
+__device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds_off_, int &walls_ok) {
+  const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
   const int e = in_.e, lane = in_.lane;
   char *base = d2d_lds + in_.off;
@@ -2576,7 +2387,7 @@ __device__ D2D_PH_ATTR int ph_plan_act(const ClosedArgs *ap, int e_, int lds_off
   }
   double4 w_head;
   int wk = __builtin_amdgcn_readfirstlane(walls_ok);
-  if constexpr (kPhaseLaunder) asm volatile("; phase" : "+s"(wk));
+  asm volatile("; phase" : "+s"(wk));
   const bool need = plan_env_quick(c, a->s, a->p, e, lane, base, &w_head, &wk);
   walls_ok = __builtin_amdgcn_readfirstlane(wk);
   if (need) {
@@ -2605,12 +2416,12 @@ __device__ D2D_PH_ATTR int ph_plan_act(const ClosedArgs *ap, int e_, int lds_off
 // `done_`: the env's episode flag as the caller knows it (the act phase of the step before returns it) -- no load, no round trip,
 // before the gaze stage can ask for anything else.  Returns the flag as this call's collision stage wrote it (-1: it did not run).
 template <int SPEC, uint32_t STAGES>
-__device__ D2D_PH_ATTR int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_off_, int t_, int done_) {
-  const PhaseIn in_ = phase_enter<kPhaseLaunder>(ap, e_, lds_off_);
+__device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_off_, int t_, int done_) {
+  const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
   const int e = in_.e, lane = in_.lane;
   int tstep = __builtin_amdgcn_readfirstlane(t_), known_done = __builtin_amdgcn_readfirstlane(done_);
-  if constexpr (kPhaseLaunder) asm volatile("; phase" : "+s"(tstep), "+s"(known_done));
+  asm volatile("; phase" : "+s"(tstep), "+s"(known_done));
   char *base = d2d_lds + in_.off;
   d2d_cfg c = a->c;
   if (!spec_generic(SPEC)) spec_default_apply(c);
@@ -2642,8 +2453,8 @@ __device__ D2D_PH_ATTR int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_
 }
 
 template <int SPEC, uint32_t STAGES>
-__device__ D2D_PH_ATTR int ph_stages(const ClosedArgs *ap, int e_, int lds_off_) {
-  const PhaseIn in_ = phase_enter<kPhaseLaunder>(ap, e_, lds_off_);
+__device__ __forceinline__ int ph_stages(const ClosedArgs *ap, int e_, int lds_off_) {
+  const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
   const int e = in_.e, lane = in_.lane;
   char *base = d2d_lds + in_.off;
@@ -2752,13 +2563,39 @@ void lds_optin(K kernel, size_t bytes) {
   if (bytes > LDS_SOFT) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
-// does this configuration take the specialised kernels (default geometry: grids staged whole in LDS)?
-bool spec_path(const d2d_cfg &c) {
-#ifndef D2D_NO_SPEC
-  return spec_default_matches(c);
-#else
-  return false;
-#endif
+// the tail of every launch
+int launched() {
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : fail(-3, hipGetErrorString(err));
+}
+
+// one wave per env, `wpb` of them per workgroup
+dim3 env_grid(int B, int wpb = WAVES_PER_BLOCK) { return dim3((B + wpb - 1) / wpb); }
+dim3 env_block(int wpb = WAVES_PER_BLOCK) { return dim3(WAVE * wpb); }
+
+// The instantiation of k_stages / k_closed a configuration takes: 1-3 the default geometry (spec_ncap), else the generic kernel
+// on row-major (0) or tiled (4) grids
+int spec_of(const d2d_cfg &c) {
+  if (!spec_default_matches(c)) return c.grid_tile ? 4 : 0;
+  return c.N <= spec_ncap(1) ? 1 : (c.N <= spec_ncap(2) ? 2 : 3);
+}
+
+// The code object holds the instantiations in the order the host code first names them.  They are named here once, in the order it
+// has held them since there were five, so that its bytes do not depend on the dispatch below.
+[[maybe_unused]] const void *const kInstantiationOrder[] = {
+    (const void *)k_stages<3>, (const void *)k_stages<1>, (const void *)k_stages<2>, (const void *)k_stages<4>, (const void *)k_stages<0>,
+    (const void *)k_closed<0>, (const void *)k_closed<4>, (const void *)k_closed<3>, (const void *)k_closed<1>, (const void *)k_closed<2>};
+
+// f(IntC<spec>{}): the run-time `spec` as a compile-time constant
+template <typename F>
+auto with_spec(int spec, F f) {
+  switch (spec) {
+    case 1: return f(IntC<1>{});
+    case 2: return f(IntC<2>{});
+    case 3: return f(IntC<3>{});
+    case 4: return f(IntC<4>{});
+    default: return f(IntC<0>{});
+  }
 }
 
 // Envs (waves) per workgroup -- 4, 2 or 1 -- for a per-wave working set of bytes(wpb): the choice that puts the most waves on a
@@ -2781,9 +2618,56 @@ int best_wpb(F bytes) {
   return best;
 }
 
-int pick_wpb(const d2d_cfg &c) {
-  const bool full = spec_path(c) && spec_full(c.N <= spec_ncap(1) ? 1 : (c.N <= spec_ncap(2) ? 2 : 3));
-  return best_wpb([&](int wpb) { return make_geom(c, wpb, 0, full).wave_bytes; });
+// Waves per workgroup of the plugin kernels (k_gaze, k_plan): 4 while four working sets stay within 64 KB, else 2, else 1
+int fit_wpb(size_t wave_bytes) {
+  int wpb = WAVES_PER_BLOCK;
+  while (wpb > 1 && wave_bytes * wpb > LDS_SOFT) wpb >>= 1;
+  return wpb;
+}
+
+// What a launch of the configuration looks like -- the one answer launch_stages, d2d_closed_loop, check and d2d_launch_shape
+// share.  `p` == NULL: the step kernels (k_stages<spec>); else the persistent kernel (k_closed<spec>).
+struct Launch {
+  int spec;           // the instantiation (spec_of)
+  int wpb;            // envs (waves) per workgroup; 0: no workgroup holds the working set
+  size_t wave_bytes;  // LDS of one wave
+  size_t lds() const { return wave_bytes * wpb; }
+};
+
+Launch pick_launch(const d2d_cfg &c, const d2d_plan *p) {
+  Launch l;
+  l.spec = spec_of(c);
+  if (p) {
+    // ONE wave (env) per workgroup: the waves of a workgroup never talk to each other, but a workgroup holds its wave slots and its
+    // LDS until its SLOWEST wave has finished -- and the chains of a launch differ widely (a mean chain is 0.3-0.6 of the longest:
+    // searches, resets).  With four envs per workgroup, three slots of every workgroup with a heavy env idle until it ends; with one
+    // they go to the next env at once.  Same-call, 600 / 300: config 4 (32 768 envs) 7.98e7 -> 9.35e7, config 5 2.43e7 -> 2.74e7,
+    // config 2 at 65 536 envs 1.25e8 -> 1.32e8, at 16 384 1.08e8 -> 1.14e8; at 4096 envs (one round: every env has its slot from
+    // the start) 8.44e7 = 8.42e7.  (A k_stages launch does the same work in every wave and keeps four.)
+    // The working set is that of the largest phase.
+    l.wave_bytes = with_spec(l.spec, [&](auto S) { return (size_t)closed_wave_bytes<decltype(S)::value>(c, *p, 1); });
+    l.wpb = l.wave_bytes <= LDS_HARD ? 1 : 0;
+  } else if (spec_full(l.spec)) {
+    // the whole-grid kernels have their four waves per workgroup compiled in; the default geometry with at most 40 agents always
+    // fits (8 176 B per wave at most)
+    l.wpb = WAVES_PER_BLOCK;
+    l.wave_bytes = (size_t)make_geom(c, l.wpb, spec_ncap(l.spec), true).wave_bytes;
+  } else {
+    l.wpb = best_wpb([&](int wpb) { return make_geom(c, wpb).wave_bytes; });
+    l.wave_bytes = (size_t)make_geom(c, l.wpb).wave_bytes;
+  }
+  return l;
+}
+
+bool snapshot_complete(const d2d_state *init) {
+  return init && init->agents && init->agent_unit && init->dyn_prev && init->gt && init->dmap && init->drone && init->target &&
+         init->targets && init->counters && init->active;
+}
+
+// step t's row of the measurement noise (d2d_cfg.noise_rows; a run wraps around the rows)
+auto noise_row(const d2d_cfg *c, const d2d_state *s, int32_t t) -> decltype(s->noise) {
+  if (!s->noise || c->noise_rows <= 1) return s->noise;
+  return s->noise + (size_t)((c->noise_row0 + t) % c->noise_rows) * c->B * c->N * 2;
 }
 
 int check(const d2d_cfg *c, const d2d_state *s) {
@@ -2803,7 +2687,7 @@ int check(const d2d_cfg *c, const d2d_state *s) {
   if (!s->agents || !s->agent_unit || !s->dyn_prev || !s->gt || !s->dmap || !s->drone || !s->target || !s->targets ||
       !s->counters || !s->active || !s->hit || !s->newly || !s->flags || !s->obs_local || !s->obs_yaw)
     return fail(-1, "null state pointer");
-  if (pick_wpb(*c) == 0) return fail(-4, "N / view depth too large for the per-env LDS working set");
+  if (pick_launch(*c, nullptr).wpb == 0) return fail(-4, "N / view depth too large for the per-env LDS working set");
   return 0;
 }
 
@@ -2824,49 +2708,23 @@ int launch_stages(const d2d_cfg *c, const d2d_state *s, uint32_t stages, void *s
   ka.stages = stages;
   ka.pin = pin;
   ka.coll_out = coll_out;
-  if (spec_path(*c) && c->N > spec_ncap(2)) {
-    const int wpb = pick_wpb(*c);
-    const Geom g = make_geom(*c, wpb, 0, spec_full(3));
-    const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
-    lds_optin(k_stages<3>, (size_t)g.wave_bytes * wpb);
-    hipLaunchKernelGGL(k_stages<3>, grid, block, (size_t)g.wave_bytes * wpb, (hipStream_t)stream, ka);
-  } else if (spec_path(*c)) {
-    const int spec = c->N <= spec_ncap(1) ? 1 : 2;
-    const Geom g = make_geom(*c, WAVES_PER_BLOCK, spec_ncap(spec), spec_full(spec));
-    const dim3 grid((c->B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(WAVE * WAVES_PER_BLOCK);
-    const size_t lds = (size_t)g.wave_bytes * WAVES_PER_BLOCK;
-    if (spec == 1) hipLaunchKernelGGL(k_stages<1>, grid, block, lds, (hipStream_t)stream, ka);
-    else hipLaunchKernelGGL(k_stages<2>, grid, block, lds, (hipStream_t)stream, ka);
-  } else {
-    const int wpb = pick_wpb(*c);
-    const Geom g = make_geom(*c, wpb);
-    const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
-    if (c->grid_tile) {
-      lds_optin(k_stages<4>, (size_t)g.wave_bytes * wpb);
-      hipLaunchKernelGGL(k_stages<4>, grid, block, (size_t)g.wave_bytes * wpb, (hipStream_t)stream, ka);
-    } else {
-      lds_optin(k_stages<0>, (size_t)g.wave_bytes * wpb);
-      hipLaunchKernelGGL(k_stages<0>, grid, block, (size_t)g.wave_bytes * wpb, (hipStream_t)stream, ka);
-    }
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  const Launch l = pick_launch(*c, nullptr);
+  with_spec(l.spec, [&](auto S) {
+    constexpr int SPEC = decltype(S)::value;
+    lds_optin(k_stages<SPEC>, l.lds());
+    hipLaunchKernelGGL(k_stages<SPEC>, env_grid(c->B, l.wpb), env_block(l.wpb), l.lds(), (hipStream_t)stream, ka);
+  });
+  return launched();
 }
 
 int reset_launch(const d2d_cfg *c, const d2d_state *s, const d2d_state *init, const uint8_t *mask, int mask_stride,
                  void *stream) {
   int rc = check(c, s);
   if (rc) return rc;
-  if (!init || !init->agents || !init->agent_unit || !init->dyn_prev || !init->gt || !init->dmap || !init->drone ||
-      !init->target || !init->targets || !init->counters || !init->active)
-    return fail(-1, "reset: incomplete snapshot");
+  if (!snapshot_complete(init)) return fail(-1, "reset: incomplete snapshot");
   if (c->B == 0) return 0;
-  const dim3 grid((c->B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(WAVE * WAVES_PER_BLOCK);
-  hipLaunchKernelGGL(k_reset, grid, block, 0, (hipStream_t)stream, *c, *s, *init, mask, mask_stride);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  hipLaunchKernelGGL(k_reset, env_grid(c->B), env_block(), 0, (hipStream_t)stream, *c, *s, *init, mask, mask_stride);
+  return launched();
 }
 
 int plan_check(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p) {
@@ -2933,45 +2791,43 @@ int plan_check(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p) {
 int gaze_launch(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, const d2d_state *init, bool skip_done, void *stream) {
   if ((p->gaze == D2D_GAZE_NONE && !init) || c->B == 0) return 0;
   const size_t wb = p->gaze == D2D_GAZE_OXFORD ? (size_t)gaze_geom(*c, *p).wave_bytes : 0;
-  int wpb = WAVES_PER_BLOCK;
-  while (wpb > 1 && wb * wpb > LDS_SOFT) wpb >>= 1;
-  const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
+  const int wpb = fit_wpb(wb);
+  const dim3 grid = env_grid(c->B, wpb), block = env_block(wpb);
   const size_t lds = wb * wpb;
   if (init && c->sigma != 0.0 && s->rng && init->rng)
-    hipLaunchKernelGGL(k_rng_reset_done, dim3((c->B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), dim3(WAVE * WAVES_PER_BLOCK), 0,
-                       (hipStream_t)stream, *c, *s, *init);
+    hipLaunchKernelGGL(k_rng_reset_done, env_grid(c->B), env_block(), 0, (hipStream_t)stream, *c, *s, *init);
   if (p->gaze == D2D_GAZE_OWL) {
     hipLaunchKernelGGL(k_gaze_owl, grid, block, 0, (hipStream_t)stream, *c, *s, *p, init ? *init : *s, init ? 1 : (skip_done ? 2 : 0));
   } else {
     lds_optin(k_gaze, lds);
     hipLaunchKernelGGL(k_gaze, grid, block, lds, (hipStream_t)stream, *c, *s, *p, init ? *init : *s, init ? 1 : (skip_done ? 2 : 0));
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  return launched();
 }
 
 int plan_launch(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, bool skip_done, void *stream) {
   if (p->planner != D2D_PLAN_PRIMITIVE || c->B == 0) return 0;
   const size_t wb = (size_t)plan_wave_bytes(c->N, p->nu, p->n_sample, c->W, c->H);
-  int wpb = WAVES_PER_BLOCK;
-  while (wpb > 1 && wb * wpb > LDS_SOFT) wpb >>= 1;
-  const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
-  const size_t lds = wb * wpb;
-  lds_optin(k_plan, lds);
-  hipLaunchKernelGGL(k_plan, grid, block, lds, (hipStream_t)stream, *c, *s, *p, skip_done ? 1 : 0);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  const int wpb = fit_wpb(wb);
+  lds_optin(k_plan, wb * wpb);
+  hipLaunchKernelGGL(k_plan, env_grid(c->B, wpb), env_block(wpb), wb * wpb, (hipStream_t)stream, *c, *s, *p, skip_done ? 1 : 0);
+  return launched();
 }
 
 int plan_reset_launch(const d2d_cfg *c, const d2d_plan *p, const uint8_t *mask, int mask_stride, void *stream) {
   if (c->B == 0) return 0;
-  const dim3 grid((c->B + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(WAVE * WAVES_PER_BLOCK);
-  hipLaunchKernelGGL(k_plan_reset, grid, block, 0, (hipStream_t)stream, *c, *p, mask, mask_stride);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  hipLaunchKernelGGL(k_plan_reset, env_grid(c->B), env_block(), 0, (hipStream_t)stream, *c, *p, mask, mask_stride);
+  return launched();
+}
+
+// The element-wise test hooks: kernel(args..., n) over n elements.  `bad`: the entry point's own argument test.
+template <typename K, typename... A>
+int launch_array(K kernel, int64_t n, bool bad, const char *msg, void *stream, A... args) {
+  if (n < 0 || bad) return fail(-1, msg);
+  if (n == 0) return 0;
+  const int bs = 256;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, args..., (long long)n);
+  return launched();
 }
 
 }  // namespace
@@ -3023,7 +2879,7 @@ int d2d_rollout(const d2d_cfg *c, const d2d_state *s, int32_t nsteps, const doub
   for (int32_t t = 0; t < nsteps; ++t) {
     st.action = (const double D2D_AS *)(actions + (size_t)t * c->B);
     if (wp_steps) st.wp = (const double D2D_AS *)(wp_steps + (size_t)t * c->B * 6);
-    if (s->noise && c->noise_rows > 1) st.noise = s->noise + (size_t)((c->noise_row0 + t) % c->noise_rows) * c->B * c->N * 2;
+    st.noise = noise_row(c, s, t);
     rc = launch_stages(c, &st, D2D_ST_ALL, stream, pin, coll_out ? coll_out + (size_t)t * c->B : nullptr);
     if (rc) return rc;
   }
@@ -3060,56 +2916,30 @@ int d2d_closed_loop(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, int
   if (nsteps < 0) return fail(-1, "closed_loop: bad step count");
   if (on_done < D2D_DONE_CONTINUE || on_done > D2D_DONE_FREEZE) return fail(-1, "closed_loop: bad on_done");
   const bool auto_reset = on_done == D2D_DONE_RESET;
-  if (auto_reset && (!init || !init->agents || !init->agent_unit || !init->dyn_prev || !init->gt || !init->dmap ||
-                     !init->drone || !init->target || !init->targets || !init->counters || !init->active))
-    return fail(-1, "closed_loop: D2D_DONE_RESET needs the snapshot");
+  if (auto_reset && !snapshot_complete(init)) return fail(-1, "closed_loop: D2D_DONE_RESET needs the snapshot");
   if (c->B == 0 || nsteps == 0) return 0;
-#ifndef D2D_NO_PERSISTENT
   if (c->planner_mode == D2D_PLANNER_EXTERNAL && p->launch_args && (p->planner == D2D_PLAN_PRIMITIVE || p->gaze != D2D_GAZE_NONE)) {
-    // one persistent launch: every wave loops over the steps of its own env.  Specialisation as for the step kernel;
-    // as many envs (waves) per workgroup as the largest phase's LDS working set allows
-    const int spec = !spec_path(*c) ? 0 : (c->N <= spec_ncap(1) ? 1 : (c->N <= spec_ncap(2) ? 2 : 3));
-    auto bytes = [&](int wpb) {
-      return spec == 0 ? closed_wave_bytes<0>(*c, *p, wpb) : spec == 1 ? closed_wave_bytes<1>(*c, *p, wpb)
-           : spec == 2 ? closed_wave_bytes<2>(*c, *p, wpb) : closed_wave_bytes<3>(*c, *p, wpb);
-    };
-    // ONE wave (env) per workgroup: the waves of a workgroup never talk to each other, but a workgroup holds its wave slots and its
-    // LDS until its SLOWEST wave has finished -- and the chains of a launch differ widely (a mean chain is 0.3-0.6 of the longest:
-    // searches, resets).  With four envs per workgroup, three slots of every workgroup with a heavy env idle until it ends; with one
-    // they go to the next env at once.  Same-call, 600 / 300: config 4 (32 768 envs) 7.98e7 -> 9.35e7, config 5 2.43e7 -> 2.74e7,
-    // config 2 at 65 536 envs 1.25e8 -> 1.32e8, at 16 384 1.08e8 -> 1.14e8; at 4096 envs (one round: every env has its slot from
-    // the start) 8.44e7 = 8.42e7.  (A k_stages launch does the same work in every wave and keeps four.)
-    const int wpb = (size_t)bytes(1) <= LDS_HARD ? 1 : 0;
-    if (wpb >= 1) {
-      const dim3 grid((c->B + wpb - 1) / wpb), block(WAVE * wpb);
-      const size_t lds = (size_t)bytes(wpb) * wpb;
+    // one persistent launch: every wave loops over the steps of its own env.  Specialisation as for the step kernel
+    const Launch l = pick_launch(*c, p);
+    if (l.wpb >= 1) {
       ClosedArgs *dev = (ClosedArgs *)p->launch_args;
       hipLaunchKernelGGL(k_closed_args, dim3(1), dim3(64), 0, (hipStream_t)stream, dev, *c, *s, *p, auto_reset ? *init : *s,
                          (int)on_done, (int)nsteps);
-      if (spec == 0) lds_optin(k_closed<0>, lds), lds_optin(k_closed<4>, lds);
-      if (spec == 3) lds_optin(k_closed<3>, lds);
-      switch (spec) {
-        case 0:
-          if (c->grid_tile) hipLaunchKernelGGL(k_closed<4>, grid, block, lds, (hipStream_t)stream, (const ClosedArgs *)dev);
-          else hipLaunchKernelGGL(k_closed<0>, grid, block, lds, (hipStream_t)stream, (const ClosedArgs *)dev);
-          break;
-        case 1: hipLaunchKernelGGL(k_closed<1>, grid, block, lds, (hipStream_t)stream, (const ClosedArgs *)dev); break;
-        case 2: hipLaunchKernelGGL(k_closed<2>, grid, block, lds, (hipStream_t)stream, (const ClosedArgs *)dev); break;
-        default: hipLaunchKernelGGL(k_closed<3>, grid, block, lds, (hipStream_t)stream, (const ClosedArgs *)dev); break;
-      }
-      hipError_t err = hipGetLastError();
-      if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-      return 0;
+      with_spec(l.spec, [&](auto S) {
+        constexpr int SPEC = decltype(S)::value;
+        lds_optin(k_closed<SPEC>, l.lds());
+        hipLaunchKernelGGL(k_closed<SPEC>, env_grid(c->B, l.wpb), env_block(l.wpb), l.lds(), (hipStream_t)stream, (const ClosedArgs *)dev);
+      });
+      return launched();
     }
   }
-#endif
   // any other configuration: one launch per stage per step (4 per step, 2 when the planner stage is not on the device)
   const bool split = p->planner == D2D_PLAN_PRIMITIVE;
   const uint32_t skip = on_done == D2D_DONE_FREEZE ? D2D_ST_SKIP_DONE : 0;
   for (int32_t t = 0; t < nsteps; ++t) {
     if ((rc = gaze_launch(c, s, p, auto_reset ? init : nullptr, skip != 0, stream))) return rc;
     d2d_state sn = *s;  // this step's row of the measurement noise
-    if (s->noise && c->noise_rows > 1) sn.noise = s->noise + (size_t)((c->noise_row0 + t) % c->noise_rows) * c->B * c->N * 2;
+    sn.noise = noise_row(c, s, t);
     if (split) {
       if ((rc = launch_stages(c, &sn, D2D_ST_PERCEIVE | skip, stream))) return rc;
       if ((rc = plan_launch(c, s, p, skip != 0, stream))) return rc;
@@ -3124,87 +2954,41 @@ int d2d_closed_loop(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, int
 int d2d_launch_shape(const d2d_cfg *c, const d2d_plan *p, int32_t out[4]) {
   if (!c || !out) return fail(-1, "launch_shape: null argument");
   if (c->abi_version != D2D_ABI_VERSION) return fail(-2, "ABI version mismatch");
-  const int spec = !spec_path(*c) ? 0 : (c->N <= spec_ncap(1) ? 1 : (c->N <= spec_ncap(2) ? 2 : 3));
-  const bool full = spec_full(spec);
-  int wpb = (spec == 1 || spec == 2) ? WAVES_PER_BLOCK : pick_wpb(*c);
-  size_t wb = 0;
-  if (!p) {
-    wb = wpb ? (size_t)make_geom(*c, wpb, spec_ncap(spec), full).wave_bytes : 0;
-  } else {
-    auto bytes = [&](int w) {
-      return spec == 0 ? closed_wave_bytes<0>(*c, *p, w) : spec == 1 ? closed_wave_bytes<1>(*c, *p, w)
-           : spec == 2 ? closed_wave_bytes<2>(*c, *p, w) : closed_wave_bytes<3>(*c, *p, w);
-    };
-    wpb = (size_t)bytes(1) <= LDS_HARD ? 1 : 0;   // the persistent kernel runs one env per workgroup (d2d_closed_loop)
-    wb = wpb >= 1 ? (size_t)bytes(wpb) : 0;
-    if (!p->launch_args || c->planner_mode != D2D_PLANNER_EXTERNAL) wpb = 0;
-  }
-  out[0] = wpb;
-  out[1] = (int32_t)(wb * (size_t)(wpb > 0 ? wpb : 0));
+  Launch l = pick_launch(*c, p);
+  // (with a plan: what d2d_closed_loop launches when it takes the persistent kernel, which needs launch_args and an external planner)
+  if (p && (!p->launch_args || c->planner_mode != D2D_PLANNER_EXTERNAL)) l.wpb = 0;
+  out[0] = l.wpb;
+  out[1] = (int32_t)l.lds();
   out[2] = out[1] > 0 ? (int32_t)(LDS_HARD / (size_t)out[1]) : 0;
-  out[3] = full ? 1 : 0;
+  out[3] = spec_full(l.spec) ? 1 : 0;
   return 0;
 }
 
 int d2d_sincos_array(const double *in, double *so, double *co, int64_t n, void *stream) {
-  if (n < 0 || (n > 0 && (!in || !so || !co))) return fail(-1, "sincos_array: bad arguments");
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(k_sincos, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, in, so, co,
-                     (long long)n);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  return launch_array(k_sincos, n, n > 0 && (!in || !so || !co), "sincos_array: bad arguments", stream, in, so, co);
 }
 
 int d2d_tan_array(const double *in, double *out, int64_t n, void *stream) {
-  if (n < 0 || (n > 0 && (!in || !out))) return fail(-1, "tan_array: bad arguments");
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(k_tan, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, in, out,
-                     (long long)n);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  return launch_array(k_tan, n, n > 0 && (!in || !out), "tan_array: bad arguments", stream, in, out);
 }
 
 int d2d_atan2_array(const double *y, const double *x, double *out, int64_t n, void *stream) {
-  if (n < 0 || (n > 0 && (!y || !x || !out))) return fail(-1, "atan2_array: bad arguments");
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(k_atan2, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, y, x, out, (long long)n);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  return launch_array(k_atan2, n, n > 0 && (!y || !x || !out), "atan2_array: bad arguments", stream, y, x, out);
 }
 
-int d2d_log_array(const double *x, double *out, int64_t n, void *stream) {
-  if (!x || !out || n < 0) return fail(-1, "log_array: bad argument");
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(k_log, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, x, out, (long long)n);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+int d2d_log_array(const double *x, double *out, int64_t n, void *stream) {  // (null pointers are refused at n == 0 too)
+  return launch_array(k_log, n, !x || !out, "log_array: bad argument", stream, x, out);
+}
+
+int d2d_pow2_array(const double *x, double *out, int64_t n, void *stream) {
+  return launch_array(k_pow2, n, n > 0 && (!x || !out), "pow2_array: bad arguments", stream, x, out);
 }
 
 int d2d_rng_draw(uint32_t *rng, const int32_t *m, double *out, int32_t B, int32_t max_m, void *stream) {
   if (!rng || !m || !out || B < 0 || max_m < 0) return fail(-1, "rng_draw: bad argument");
   if (B == 0) return 0;
   hipLaunchKernelGGL(k_rng_draw, dim3((unsigned)B), dim3(WAVE), 0, (hipStream_t)stream, rng, m, out, max_m);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
-}
-
-int d2d_pow2_array(const double *x, double *out, int64_t n, void *stream) {
-  if (n < 0 || (n > 0 && (!x || !out))) return fail(-1, "pow2_array: bad arguments");
-  if (n == 0) return 0;
-  const int bs = 256;
-  hipLaunchKernelGGL(k_pow2, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, (hipStream_t)stream, x, out, (long long)n);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(-3, hipGetErrorString(err));
-  return 0;
+  return launched();
 }
 
 }  // extern "C"

@@ -1444,11 +1444,8 @@ __device__ __forceinline__ double owl_unseen(double theta, double half, double h
 // two-element dot and norm are fma(b1, b2, a1 * a2), `f[i, :].dot(lamb)` is a chain of five FMAs from 0, `** 2` is libm's
 // pow(x, 2.0) (d2d_pow2.h).  A drone at rest makes d_v NaN, hence every cost NaN, hence candidate 0: nothing here special-cases
 // it.  The per-stage launch runs this stage in a kernel of its own (k_gaze_owl), so that k_gaze keeps its allocation.
-#ifndef D2D_OWL_ATTR
-#define D2D_OWL_ATTR __forceinline__
-#endif
-__device__ D2D_OWL_ATTR void owl_gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, int e, int lane,
-                                                       double x0, double y0, double yaw) {
+__device__ __forceinline__ void owl_gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, int e, int lane,
+                                             double x0, double y0, double yaw) {
   const double D2D_AS *__restrict__ tab = p.owl_tab;
   double D2D_AS *st = p.owl_state + (size_t)e * D2D_OWL_STATE_F;
   double *act = (double *)s.action;
@@ -1656,19 +1653,6 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
   }
   // ---- the seven view directions in one pass: lane a < n_yaw = candidate a, lane 7 = the current pose (:71, :114) ----
   double *vdir = stk;  // [8][2], free until the add stacks are used
-#ifdef D2D_SINCOS_TWO_PASS
-  if (lane < 8) {
-    double cyv = 0.0, syv = 0.0;
-    if (lane < p.n_yaw || lane == 7) {
-      // Drone2D.__init__ takes `yaw % 360` for the candidates (utils.py:718); the drone's own yaw already is
-      const double ty = (lane == 7) ? yaw : py_mod360(yaw + ys_l * c.dt);
-      cyv = d2d_cos(ty * deg2rad);
-      syv = -d2d_sin(ty * deg2rad);
-    }
-    vdir[2 * lane] = cyv;
-    vdir[2 * lane + 1] = syv;
-  }
-#else
   // lanes 0..7 the cosines, lanes 8..15 the (negated) sines of the same eight angles: one walk through the sin / cos code for both
   // (d2d_sin_or_cos: each lane does what d2d_cos / d2d_sin do for its argument, bit for bit)
   if (lane < 16) {
@@ -1682,7 +1666,6 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
     }
     vdir[2 * a + (lane >> 3)] = v;
   }
-#endif
   // the largest yaw step of a candidate, degrees: a maximum over the lanes that hold the rates (exact in any order)
   double span_deg;
   {

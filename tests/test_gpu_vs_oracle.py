@@ -120,6 +120,39 @@ def test_rollout_and_reset_on_device(pkg, hip, oracle):
     _assert_same(dev, ref, 'step after reset')
 
 
+_OTHER_VIEW = dict(drone_view_range=120, drone_view_depth=60)
+
+
+@pytest.mark.parametrize('label,whole,kw', [
+    ('N16', 1, dict(agent_number=16)), ('N17', 1, dict(agent_number=17)),
+    ('N40', 1, dict(agent_number=40)), ('N41', 0, dict(agent_number=41)),
+    ('N17_rowmajor_600x450', 0, dict(agent_number=17, map_size=[600, 450], init_pos=[300, 220], target_list=[[520, 380]], **_OTHER_VIEW)),
+    ('N17_tiled_530x470', 0, dict(agent_number=17, map_size=[530, 470], init_pos=[450, 60], target_list=[[80, 400]],
+                                  grid_layout='tiled', **_OTHER_VIEW)),
+])
+def test_step_and_rollout_at_the_dispatch_boundaries(pkg, hip, oracle, label, whole, kw):
+    """The agent counts on either side of the step kernels' specialisations (16 | 17, 40 | 41 on the default geometry) and 17 agents
+    on the two generic kernels (another row-major map; tiles whose edge tiles are partial): a wrong instantiation, workgroup
+    size or LDS size shows here.  d2d_step and a 4-step d2d_rollout with pinned positions and the collision output, every field."""
+    from drone2d_amd import _lib
+    B = 3
+    dev, ref = _pair(pkg, hip, oracle, B, agent_radius=8, agent_max_speed=40, map_id=61, **kw)
+    assert dev.cfg.N == kw['agent_number'] and _lib.launch_shape(dev.cfg)[3] == whole
+    assert dev.cfg.grid_tile == (16 if 'tiled' in label else 0)
+    rng = np.random.RandomState(dev.cfg.N)
+    a = rng.uniform(-1, 1, B)
+    dev.step(a)
+    ref.step(a)
+    _assert_same(dev, ref, f'{label}: step')
+    acts = rng.uniform(-1, 1, (4, B))
+    pin = np.stack([rng.randint(30, int(dev.cfg.W_px) - 30, B), rng.randint(30, int(dev.cfg.H_px) - 30, B)], 1).astype(np.float64)
+    cd = dev.rollout(acts, pin=pin, collisions=True)
+    cr = ref.rollout(acts, pin=pin, collisions=True)
+    dev.sync()
+    assert torch.equal(cd.cpu(), cr)
+    _assert_same(dev, ref, f'{label}: rollout')
+
+
 @pytest.mark.parametrize('label,B,kw', [
     ('config3', 65536, dict(agent_number=50, agent_radius=10, agent_max_speed=40, map_id=0, static_map='maps/random_map_0.npy')),
     ('config4_shard', 32768, dict(agent_number=10, agent_radius=15, agent_max_speed=20, map_id=1, static_map='maps/obstacle_map.npy')),
