@@ -148,8 +148,10 @@ def bind_worlds(lib):
 
 
 # ---- include/d2d_metrics.h: the difficulty metrics on the device (csrc/metrics/libd2d_metrics.so, its own version) ----
-D2D_METRICS_VERSION = 1
+D2D_METRICS_VERSION = 2
 VO_MAX_B, VO_MAX_P, VO_MAX_ELEMS = 65535, 64 * 65535, 0x7fffffff
+TRAV_MAX_ELEMS = 0x7fffffff
+FIT_MAX_N, FIT_MAX_P, FIT_MAX_ELEMS = 256, 64 * 65535, 0x7fffffff
 
 
 def bind_metrics(lib):
@@ -161,6 +163,8 @@ def bind_metrics(lib):
         'd2d_vo_geometry': (C.c_int, [V, V, C.c_double, I, I, I, V, V, V, V]),
         'd2d_vo_cones': (C.c_int, [V, V, V, I, I, I, V, V]),
         'd2d_vo_count': (C.c_int, [V, V, V, V, I, I, I, I, V, V]),
+        'd2d_trav_steps': (C.c_int, [V, I, I, I, V, I, V, V]),
+        'd2d_fit_first_hit': (C.c_int, [V, V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I, I, I, I, V, V, V]),
     }
     out = {}
     for name, (res, args) in sig.items():

@@ -79,6 +79,7 @@ class HipBackend:
     supports_device_noise = True          # d2d_state.rng: the tracker stage draws the measurement noise itself (var_cam != 0)
     supports_device_worlds = True         # include/d2d_worlds.h: the seeded worlds are built on the device
     supports_vo_metric = True             # include/d2d_metrics.h: the velocity-obstacle feasibility metric (metrics.py)
+    supports_difficulty_tables = True     # include/d2d_metrics.h: the traversability and survival-fit metrics (metrics.py)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -178,6 +179,18 @@ class HipBackend:
         B, P, N, _ = cone.shape
         self._metrics('vo_count', agents.data_ptr(), cand.data_ptr(), cone.data_ptr(), collided.data_ptr(), B, N, P, cand.shape[0],
                       count.data_ptr())
+
+    def trav_steps(self, gt, starts, steps):
+        """d2d_trav_steps: gt [B, W, H] uint8 (row-major), starts [S, 2] int32 (inside the grid: the caller has checked) ->
+        steps [B, S, 8] int32 (-1: the start cell is not UNOCCUPIED)"""
+        B, W, H = gt.shape
+        self._metrics('trav_steps', gt.data_ptr(), B, W, H, starts.data_ptr(), starts.shape[0], steps.data_ptr())
+
+    def fit_first_hit(self, agents, pos, drone_radius, W_px, H_px, scale, dt, checks, first, agents_out=None):
+        """d2d_fit_first_hit: agents [B, 6, N], pos [P, 2] -> first [B, P] int32 (-1: never hit), agents_out [B, 6, N] or None"""
+        B, _, N = agents.shape
+        self._metrics('fit_first_hit', agents.data_ptr(), pos.data_ptr(), float(drone_radius), float(W_px), float(H_px), float(scale),
+                      float(dt), B, N, pos.shape[0], int(checks), first.data_ptr(), None if agents_out is None else agents_out.data_ptr())
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -1,6 +1,7 @@
-// d2d_metrics.hip — the velocity-obstacle feasibility metric on the device (gfx950): kernels + the C entry points of
-// include/d2d_metrics.h.  Its own library (libd2d_metrics.so): it shares no kernel with the step, the closed loop or the worlds.
+// d2d_metrics.hip — the difficulty metrics on the device (gfx950): kernels + the C entry points of include/d2d_metrics.h.  Its own
+// library (libd2d_metrics.so): it shares no kernel with the step, the closed loop or the worlds.
 //
+// The velocity-obstacle feasibility metric:
 //   geometry    thread = (world, position, agent): arg and theta_ba, coalesced; a second small kernel, thread = (world, position),
 //               ORs the collision test over the agents.
 //   cones       thread = (world, position, agent): two sin, two cos, two atan2.
@@ -12,7 +13,18 @@
 //               capped.  A setup kernel writes 0 / -1 to every count first; the waves add their popcounts (integer atomics: the
 //               order cannot change the sum).
 //
-// Arithmetic is fp64 in the reference's own operation order (d2d_vo.h), compiled with -ffp-contract=off.
+//
+// Traversability:
+//   trav_steps  one workgroup per world; the grid is staged in LDS when it has at most TRAV_LDS cells and read from global memory
+//               otherwise; thread = (start, direction), in as many passes as 8 * S needs.  Integers only.
+//
+// Survival fit:
+//   fit_first_hit  one wave per (world, 64 positions).  Lane = agent for the updates: the state of up to four tiles of 64 agents
+//               stays in registers over all steps.  Lane = position for the tests: position, radius sum of one agent at a time reach
+//               every lane through readlane.  No LDS, no barrier, no atomics; the waves of a world's further position tiles repeat
+//               the (cheap) agent updates, the first one writes agents_out.
+//
+// Arithmetic is fp64 in the reference's own operation order (d2d_vo.h, d2d_difficulty.h), compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -24,11 +36,16 @@
 #define D2D_ATAN2_QUAL __device__ __forceinline__
 #define D2D_ATAN2_TBL_QUAL __device__ const
 #include "d2d_vo.h"
+#define D2D_DF_QUAL __device__ __forceinline__
+#include "d2d_difficulty.h"
 
 #define WAVE 64
 #define VO_TILE 32   /* agents per LDS tile of theta_dif: 32 * 64 * 8 B = 16 KB; 2 * VO_TILE cone doubles = one per lane */
 #define VO_PCH 64    /* positions per wave: lane l keeps position l's mask between the tiles */
 #define EW_BLOCK 256
+#define TRAV_BLOCK 256
+#define TRAV_LDS 16384 /* cells of a grid that is staged in LDS (16 KB: 128 x 128); a larger one is read from global memory */
+#define FIT_TILES (D2D_FIT_MAX_N / WAVE)
 
 namespace {
 
@@ -135,6 +152,79 @@ __global__ __launch_bounds__(WAVE) void vo_count_kernel(const double *__restrict
   if (mine) atomicAdd(count + bp0 + lane, (int32_t)__popcll(mask));
 }
 
+template <bool STAGED>
+__global__ __launch_bounds__(TRAV_BLOCK) void trav_steps_kernel(const uint8_t *__restrict__ gt, int W, int H, const int32_t *__restrict__ starts,
+                                                               int S, int32_t *__restrict__ steps) {
+  __shared__ uint8_t cells[STAGED ? TRAV_LDS : 4];
+  const uint8_t *g = gt + (size_t)blockIdx.x * W * H;
+  if constexpr (STAGED) {
+    const int n = W * H;                        // <= TRAV_LDS
+    for (int c = threadIdx.x; c < n; c += TRAV_BLOCK) cells[c] = g[c];
+    __syncthreads();
+  }
+  const uint8_t *grid = STAGED ? cells : g;
+  int32_t *out = steps + (size_t)blockIdx.x * S * 8;
+  for (int t = threadIdx.x; t < 8 * S; t += TRAV_BLOCK) {
+    const int i = starts[2 * (t >> 3)], j = starts[2 * (t >> 3) + 1];
+    out[t] = d2d_trav_open(grid, W, H, i, j) ? d2d_trav_ray(grid, W, H, i, j, t & 7) : -1;
+  }
+}
+
+template <int NT>   // tiles of 64 agents: 64 * (NT - 1) < N <= 64 * NT
+__global__ __launch_bounds__(WAVE) void fit_first_hit_kernel(const double *__restrict__ agents, const double *__restrict__ pos, double drone_radius,
+                                                            double W_px, double H_px, double scale, double dt, int N, int P, int checks,
+                                                            int32_t *__restrict__ first, double *__restrict__ agents_out) {
+  const int lane = threadIdx.x;
+  const long long p = (long long)blockIdx.y * WAVE + lane;
+  const double *ag = agents + (size_t)blockIdx.x * D2D_DF_AF * N;
+  double px[NT], py[NT], vx[NT], vy[NT], r[NT], rr[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int j = t * WAVE + lane;
+    const bool live = j < N;                    // lanes beyond N neither load nor store
+    px[t] = live ? ag[D2D_DF_A_PX * N + j] : 0.0;
+    py[t] = live ? ag[D2D_DF_A_PY * N + j] : 0.0;
+    vx[t] = live ? ag[D2D_DF_A_VX * N + j] : 0.0;
+    vy[t] = live ? ag[D2D_DF_A_VY * N + j] : 0.0;
+    r[t] = live ? ag[D2D_DF_A_R * N + j] : 0.0;
+    rr[t] = r[t] + drone_radius;
+  }
+  const bool mine = p < P;                      // lanes beyond P neither load nor store
+  const double ax = mine ? pos[2 * p] : 0.0, ay = mine ? pos[2 * p + 1] : 0.0;
+  int32_t f = -1;
+  for (int k = -1; k < checks; ++k) {
+    if (k >= 0 && __ballot(mine && f < 0) != 0ull) {   // (a tile whose positions have all been hit only moves the agents on)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int na = min(WAVE, N - t * WAVE);
+        for (int a = 0; a < na; ++a) {
+          const double bx = readlane_f64(px[t], a), by = readlane_f64(py[t], a), brr = readlane_f64(rr[t], a);
+          if (f < 0 && d2d_fit_hits(ax, ay, bx, by, brr)) f = k;
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      if (t * WAVE + lane < N) d2d_fit_agent_step(&px[t], &py[t], &vx[t], &vy[t], r[t], W_px, H_px, scale, dt);
+  }
+  if (mine) first[(size_t)blockIdx.x * P + p] = f;
+  if (agents_out != nullptr && blockIdx.y == 0) {
+    double *o = agents_out + (size_t)blockIdx.x * D2D_DF_AF * N;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int j = t * WAVE + lane;
+      if (j < N) {
+        o[D2D_DF_A_PX * N + j] = px[t];
+        o[D2D_DF_A_PY * N + j] = py[t];
+        o[D2D_DF_A_VX * N + j] = vx[t];
+        o[D2D_DF_A_VY * N + j] = vy[t];
+        o[D2D_DF_A_R * N + j] = r[t];
+        o[D2D_DF_A_R2 * N + j] = ag[D2D_DF_A_R2 * N + j];
+      }
+    }
+  }
+}
+
 int check_sizes(const char *who, long long B, long long N, long long P, long long C) {
   char msg[200];
   if (B < 1 || N < 1 || P < 1 || C < 1) {
@@ -197,6 +287,44 @@ int d2d_vo_count(const double *agents, const double *cand, const double *cone, c
   const dim3 grid((unsigned)(((long long)C + WAVE - 1) / WAVE), (unsigned)((P + VO_PCH - 1) / VO_PCH), (unsigned)B);
   hipLaunchKernelGGL(vo_count_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, agents, cand, cone, collided, (int)N, (int)P, (int)C, count);
   return launched("d2d_vo_count");
+}
+
+int d2d_trav_steps(const uint8_t *gt, int32_t B, int32_t W, int32_t H, const int32_t *starts, int32_t S, int32_t *steps, void *stream) {
+  if (B < 1 || W < 1 || H < 1 || S < 1) return fail(-1, "d2d_trav_steps: B, W, H, S >= 1");
+  if (!gt || !starts || !steps) return fail(-1, "d2d_trav_steps: a pointer is NULL");
+  if ((long long)W * H > D2D_TRAV_MAX_ELEMS || (long long)B * S * 8 > D2D_TRAV_MAX_ELEMS)
+    return fail(-4, "d2d_trav_steps: W * H <= 2^31 - 1 and B * S * 8 <= 2^31 - 1");
+  if ((long long)W * H <= TRAV_LDS)
+    hipLaunchKernelGGL(trav_steps_kernel<true>, dim3((unsigned)B), dim3(TRAV_BLOCK), 0, (hipStream_t)stream, gt, (int)W, (int)H, starts, (int)S,
+                       steps);
+  else
+    hipLaunchKernelGGL(trav_steps_kernel<false>, dim3((unsigned)B), dim3(TRAV_BLOCK), 0, (hipStream_t)stream, gt, (int)W, (int)H, starts, (int)S,
+                       steps);
+  return launched("d2d_trav_steps");
+}
+
+int d2d_fit_first_hit(const double *agents, const double *pos, double drone_radius, double W_px, double H_px, double scale, double dt,
+                      int32_t B, int32_t N, int32_t P, int32_t checks, int32_t *first, double *agents_out, void *stream) {
+  if (B < 1 || N < 1 || P < 1 || checks < 0) return fail(-1, "d2d_fit_first_hit: B, N, P >= 1 and checks >= 0");
+  if (!agents || !pos || !first) return fail(-1, "d2d_fit_first_hit: a pointer is NULL");
+  if (N > D2D_FIT_MAX_N || P > D2D_FIT_MAX_P || (long long)B * P > D2D_FIT_MAX_ELEMS || (long long)B * D2D_DF_AF * N > D2D_FIT_MAX_ELEMS) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "d2d_fit_first_hit: N <= %d, P <= %d and B * max(P, 6 * N) <= %d", D2D_FIT_MAX_N, D2D_FIT_MAX_P, D2D_FIT_MAX_ELEMS);
+    return fail(-4, msg);
+  }
+  const dim3 grid((unsigned)B, (unsigned)((P + WAVE - 1) / WAVE));
+#define FIT_LAUNCH(NT)                                                                                                                  \
+  hipLaunchKernelGGL(fit_first_hit_kernel<NT>, grid, dim3(WAVE), 0, (hipStream_t)stream, agents, pos, drone_radius, W_px, H_px, scale, dt, \
+                     (int)N, (int)P, (int)checks, first, agents_out)
+  static_assert(FIT_TILES == 4, "one case per tile count");
+  switch ((N + WAVE - 1) / WAVE) {
+    case 1: FIT_LAUNCH(1); break;
+    case 2: FIT_LAUNCH(2); break;
+    case 3: FIT_LAUNCH(3); break;
+    default: FIT_LAUNCH(4); break;
+  }
+#undef FIT_LAUNCH
+  return launched("d2d_fit_first_hit");
 }
 
 }  // extern "C"

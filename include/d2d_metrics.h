@@ -1,5 +1,6 @@
 /*
- * d2d_metrics.h — C ABI of the difficulty metrics on the device (libd2d_metrics.so).
+ * d2d_metrics.h — C ABI of the difficulty metrics on the device (libd2d_metrics.so): the velocity-obstacle feasibility metric,
+ * the traversability metric and the survival-fit metric of the reference's script/difficulty_calculator/.
  *
  * The velocity-obstacle feasibility metric of the reference's script/difficulty_calculator/vo_calculator.py:36-120: for a seeded
  * world (the agents' initial positions, preferred velocities and radii), a grid of drone positions and a table of candidate
@@ -24,6 +25,25 @@
  * state's own d2d_state.agents, [B][6][N] doubles (rows D2D_A_PX, PY, VX, VY, R, R2).
  *
  * Sizes: any B, N, P, C >= 1 with B <= 65535, P <= 64 * 65535 and B * P * N * 2 < 2^31 (-4 otherwise).
+ *
+ * Traversability (traversibility_calculator.py -> envs/metric_env.py:286-293 -> demos/traversibility.py:26-51): from each start cell
+ * of the ground-truth grid, the cells walked in each of eight directions while the next cell is inside the grid and UNOCCUPIED.
+ *
+ *   d2d_trav_steps    traversibility.py:32-48   the walks, counted in steps (integers only)    -> steps
+ *   (host)            :46, :51, metric_env.py:291-293   a diagonal step is math.sqrt(2), added one at a time; np.mean of the eight
+ *                     distances; the running sum over the starts
+ *
+ * Sizes: B, W, H, S >= 1 with B <= 2^31 - 1, W * H <= 2^31 - 1 and B * S * 8 <= 2^31 - 1 (-4 otherwise).
+ *
+ * Survival fit (survivability_calculator.py:13-48, the table script/fit.py fits the difficulty model to): the agents move under the
+ * constant-velocity model (envs/drone_v2.py:176-179 + utils.py:472-493, which reads neither a grid nor the drone) and every `dt` a
+ * drone standing at each of P positions is tested against every agent; the time of the first hit is the position's survival time.
+ *
+ *   d2d_fit_first_hit  :32-41   one agent update, then `checks` times (test, update)          -> first (the index of the check)
+ *   (host)             :30, :34, :40, :45-48   np.arange(0, T, 0.1)[first], min, - 0.1, the clamp, np.mean
+ *
+ * Sizes: B, N, P >= 1, checks >= 0 with B <= 2^31 - 1, N <= 256 (four tiles of 64 agents, kept in registers over all steps),
+ * P <= 64 * 65535 and B * max(P, 6 * N) <= 2^31 - 1 (-4 otherwise).
  */
 #ifndef D2D_METRICS_H
 #define D2D_METRICS_H
@@ -34,7 +54,7 @@
 extern "C" {
 #endif
 
-#define D2D_METRICS_VERSION 1
+#define D2D_METRICS_VERSION 2
 
 #define D2D_VO_MAX_B 65535           /* worlds of one call (a grid dimension) */
 #define D2D_VO_MAX_P (64 * 65535)    /* positions of one call (64 per workgroup, a grid dimension) */
@@ -59,6 +79,28 @@ int d2d_vo_cones(const double *theta_ba, const double *half, const uint8_t *coll
  * whatever the buffer held (the call sets them before its counting kernel adds to them). */
 int d2d_vo_count(const double *agents, const double *cand, const double *cone, const uint8_t *collided, int32_t B, int32_t N,
                  int32_t P, int32_t C, int32_t *count, void *stream);
+
+#define D2D_TRAV_MAX_ELEMS 0x7fffffff /* W * H, the cells of one grid; B * S * 8, the entries of `steps`; B, a grid dimension */
+#define D2D_FIT_MAX_N 256            /* agents of one world: four register tiles of 64 */
+#define D2D_FIT_MAX_P (64 * 65535)   /* positions of one call (64 per wave, a grid dimension) */
+#define D2D_FIT_MAX_ELEMS 0x7fffffff /* B * P, the entries of `first`; B * 6 * N, the doubles of `agents`; B, a grid dimension */
+
+/* gt [B][W][H] (u8, row-major: the reference's grid_map[i][j], never a tiled layout), starts [S][2] (i32: i, j) -> steps [B][S][8]
+ * (i32): the steps walked from (i, j) towards N, NE, E, SE, S, SW, W, NW = (-1,0), (-1,1), (0,1), (1,1), (1,0), (1,-1), (0,-1),
+ * (-1,-1) while the next cell is inside the grid and 2 (UNOCCUPIED); -1 in all eight when the start cell is not 2.  Every entry is
+ * written whatever the buffer held.  `starts` lives on the device, so the library cannot look at it before the launch: the CALLER
+ * refuses a start outside the grid before uploading it (metrics.trav_steps does).  The kernel reads no cell outside the grid
+ * whatever `starts` holds; a start outside it gets -1 like any other start that is not an UNOCCUPIED cell. */
+int d2d_trav_steps(const uint8_t *gt, int32_t B, int32_t W, int32_t H, const int32_t *starts, int32_t S, int32_t *steps, void *stream);
+
+/* agents [B][6][N] (not modified), pos [P][2] (x, y) -> first [B][P] (i32), agents_out [B][6][N] or NULL.  The agents are updated
+ * once; then, `checks` times, every position is tested against every agent (dist < r_j + drone_radius, dist = sqrt(fma(y, y, x * x))
+ * as in d2d_vo_geometry) and the agents are updated again.  first = the index of the first check that hit, or -1.  agents_out = the
+ * agents after the checks + 1 updates (rows PX, PY; VX, VY = pref_velocity; R and R2 copied): what the reference's env holds when
+ * env_metrics returns.  W_px, H_px, scale, dt: params.map_size, map_scale, dt.  Every entry of both outputs is written whatever the
+ * buffers held; agents_out must not overlap agents. */
+int d2d_fit_first_hit(const double *agents, const double *pos, double drone_radius, double W_px, double H_px, double scale, double dt,
+                      int32_t B, int32_t N, int32_t P, int32_t checks, int32_t *first, double *agents_out, void *stream);
 
 #ifdef __cplusplus
 }
