@@ -3,7 +3,7 @@
 Layout
   csrc/          HIP kernels + the C ABI of include/d2d.h (libd2d_hip.so)
   _abi.py        ctypes mirror of include/d2d.h
-  _lib.py        loader of libd2d_hip.so (raises if the library is missing: there is no CPU fallback)
+  _lib.py        loader of libd2d_hip.so, libd2d_worlds.so and libd2d_metrics.so (raises if one is missing: there is no CPU fallback)
   params.py      the reference's Params / argparse surface (utils.py:65-171)
   host_init.py   world construction = the reference's __init__ (seeded, bit-identical)
   state.py       device-resident batch state

@@ -92,9 +92,14 @@ def bind(lib, prefix='d2d_'):
         'rng_draw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
         'launch_shape': (C.c_int, [P(Cfg), P(Plan), P(C.c_int32 * 4)]),
     }
+    return _bind(lib, prefix, sig, OPTIONAL)
+
+
+def _bind(lib, prefix, sig, optional=()):
+    """key -> the entry point `prefix + key` of `lib` with the (restype, argtypes) of `sig` declared on it"""
     out = {}
     for name, (res, args) in sig.items():
-        if name in OPTIONAL and not hasattr(lib, prefix + name):
+        if name in optional and not hasattr(lib, prefix + name):
             continue                       # a diagnostic query older builds of the library lack (A/B runs via D2D_LIB)
         fn = getattr(lib, prefix + name)   # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
@@ -138,13 +143,7 @@ def bind_worlds(lib):
         'build': (C.c_int, [P(WorldSpec), P(State), C.c_void_p]),
         'launch_shape': (C.c_int, [P(WorldSpec), P(C.c_int32 * 2)]),
     }
-    out = {}
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, 'd2d_worlds_' + name)
-        fn.restype = res
-        fn.argtypes = args
-        out[name] = fn
-    return out
+    return _bind(lib, 'd2d_worlds_', sig)
 
 
 # ---- include/d2d_metrics.h: the difficulty metrics on the device (csrc/metrics/libd2d_metrics.so, its own version) ----
@@ -157,19 +156,12 @@ FIT_MAX_N, FIT_MAX_P, FIT_MAX_ELEMS = 256, 64 * 65535, 0x7fffffff
 def bind_metrics(lib):
     """argtypes / restypes of include/d2d_metrics.h on a loaded CDLL."""
     V, I = C.c_void_p, C.c_int32
+    own = {'version': (C.c_int, []), 'last_error': (C.c_char_p, [])}
     sig = {
-        'd2d_metrics_version': (C.c_int, []),
-        'd2d_metrics_last_error': (C.c_char_p, []),
-        'd2d_vo_geometry': (C.c_int, [V, V, C.c_double, I, I, I, V, V, V, V]),
-        'd2d_vo_cones': (C.c_int, [V, V, V, I, I, I, V, V]),
-        'd2d_vo_count': (C.c_int, [V, V, V, V, I, I, I, I, V, V]),
-        'd2d_trav_steps': (C.c_int, [V, I, I, I, V, I, V, V]),
-        'd2d_fit_first_hit': (C.c_int, [V, V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I, I, I, I, V, V, V]),
+        'vo_geometry': (C.c_int, [V, V, C.c_double, I, I, I, V, V, V, V]),
+        'vo_cones': (C.c_int, [V, V, V, I, I, I, V, V]),
+        'vo_count': (C.c_int, [V, V, V, V, I, I, I, I, V, V]),
+        'trav_steps': (C.c_int, [V, I, I, I, V, I, V, V]),
+        'fit_first_hit': (C.c_int, [V, V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I, I, I, I, V, V, V]),
     }
-    out = {}
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-        out[name.replace('d2d_metrics_', '').replace('d2d_', '')] = fn
-    return out
+    return dict(_bind(lib, 'd2d_metrics_', own), **_bind(lib, 'd2d_', sig))

@@ -21,53 +21,62 @@ def launch_shape(cfg, plan=None, fn=None):
     if fn is None:
         fn = load_library()[1]
     out = (C.c_int32 * 4)()
-    rc = fn['launch_shape'](C.byref(cfg), None if plan is None else C.byref(plan), C.byref(out))
-    if rc != 0:
-        raise D2DError(f'd2d error {rc}: {fn["last_error"]().decode()}')
+    _check(fn['launch_shape'](C.byref(cfg), None if plan is None else C.byref(plan), C.byref(out)), fn, 'd2d')
     return tuple(out)
 
 
-def load_library(path=LIB_PATH):
-    # torch first: its bundled HIP runtime has to be the one this library binds to.  Loaded the other way round the
-    # process ends up with two runtimes and every launch fails with "no ROCm-capable device is detected".
+# file name -> (binder, version entry point, the expected version's name in _abi (read at the call), noun of the mismatch text,
+# build script under gym-drone2d-activeperception_amd/csrc/)
+_LIBRARIES = {
+    'libd2d_hip.so': (A.bind, 'abi_version', 'D2D_ABI_VERSION', 'ABI', 'build.sh'),
+    'libd2d_worlds.so': (A.bind_worlds, 'version', 'D2D_WORLDS_VERSION', 'version', 'worlds/build.sh'),
+    'libd2d_metrics.so': (A.bind_metrics, 'version', 'D2D_METRICS_VERSION', 'version', 'metrics/build.sh'),
+}
+
+
+def _load(name, path):
+    binder, version_fn, version, noun, script = _LIBRARIES[name]
+    # torch first: its bundled HIP runtime has to be the one the library binds to.  Loaded the other way round the process ends up
+    # with two runtimes and every launch fails with "no ROCm-capable device is detected".
     import torch  # noqa: F401
     if not os.path.isfile(path):
-        raise D2DError(f'{path} not found: build it with gym-drone2d-activeperception_amd/csrc/build.sh '
+        raise D2DError(f'{path} not found: build it with gym-drone2d-activeperception_amd/csrc/{script} '
                        '(or __graft_entry__.build()); there is no CPU fallback')
     lib = C.CDLL(path)
-    fn = A.bind(lib, prefix='d2d_')
-    v = fn['abi_version']()
-    if v != A.D2D_ABI_VERSION:
-        raise D2DError(f'libd2d_hip.so ABI {v} != expected {A.D2D_ABI_VERSION}: rebuild')
+    fn = binder(lib)
+    v, want = fn[version_fn](), getattr(A, version)
+    if v != want:
+        raise D2DError(f'{name} {noun} {v} != expected {want}: rebuild')
     return lib, fn
+
+
+def load_library(path=LIB_PATH):
+    return _load('libd2d_hip.so', path)
 
 
 def load_worlds_library(path=WORLDS_LIB_PATH):
-    """The world construction's own library (include/d2d_worlds.h), after torch like the other one."""
-    import torch  # noqa: F401
-    if not os.path.isfile(path):
-        raise D2DError(f'{path} not found: build it with gym-drone2d-activeperception_amd/csrc/worlds/build.sh '
-                       '(or __graft_entry__.build()); there is no CPU fallback')
-    lib = C.CDLL(path)
-    fn = A.bind_worlds(lib)
-    v = fn['version']()
-    if v != A.D2D_WORLDS_VERSION:
-        raise D2DError(f'libd2d_worlds.so version {v} != expected {A.D2D_WORLDS_VERSION}: rebuild')
-    return lib, fn
+    """The world construction's own library (include/d2d_worlds.h)."""
+    return _load('libd2d_worlds.so', path)
 
 
 def load_metrics_library(path=METRICS_LIB_PATH):
-    """The difficulty metrics' own library (include/d2d_metrics.h), after torch like the other ones."""
-    import torch  # noqa: F401
-    if not os.path.isfile(path):
-        raise D2DError(f'{path} not found: build it with gym-drone2d-activeperception_amd/csrc/metrics/build.sh '
-                       '(or __graft_entry__.build()); there is no CPU fallback')
-    lib = C.CDLL(path)
-    fn = A.bind_metrics(lib)
-    v = fn['version']()
-    if v != A.D2D_METRICS_VERSION:
-        raise D2DError(f'libd2d_metrics.so version {v} != expected {A.D2D_METRICS_VERSION}: rebuild')
-    return lib, fn
+    """The difficulty metrics' own library (include/d2d_metrics.h)."""
+    return _load('libd2d_metrics.so', path)
+
+
+def _check(rc, fn, label):
+    if rc != 0:
+        raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
+
+
+def backend_for(backend, device, flag=None, lacks=None):
+    """`backend`, or the HIP backend of `device` where it is None (which raises if a library or the GPU is missing).  With `flag`
+    (a supports_* attribute) a backend without it is refused: NotImplementedError('<its name> <lacks>')."""
+    if backend is None:
+        backend = HipBackend(device)
+    if flag is not None and not getattr(backend, flag, False):
+        raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} {lacks}')
+    return backend
 
 
 class HipBackend:
@@ -95,8 +104,7 @@ class HipBackend:
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     def _chk(self, rc):
-        if rc != 0:
-            raise D2DError(f'd2d error {rc}: {self.fn["last_error"]().decode()}')
+        _check(rc, self.fn, 'd2d')
 
     def run_stages(self, cfg, st, stages):
         self._chk(self.fn['run_stages'](C.byref(cfg), C.byref(st), stages, self._stream()))
@@ -152,16 +160,12 @@ class HipBackend:
 
     def build_worlds(self, spec, st):
         """d2d_worlds_build: fill the world fields behind `st` for the envs of `spec` (vec_env.world_spec) on the current stream"""
-        rc = self.wfn['build'](C.byref(spec), C.byref(st), self._stream())
-        if rc != 0:
-            raise D2DError(f'd2d_worlds error {rc}: {self.wfn["last_error"]().decode()}')
+        _check(self.wfn['build'](C.byref(spec), C.byref(st), self._stream()), self.wfn, 'd2d_worlds')
 
     def _metrics(self, name, *args):
         if self.mfn is None:
             self.mlib, self.mfn = load_metrics_library()
-        rc = self.mfn[name](*args, self._stream())
-        if rc != 0:
-            raise D2DError(f'd2d_metrics error {rc}: {self.mfn["last_error"]().decode()}')
+        _check(self.mfn[name](*args, self._stream()), self.mfn, 'd2d_metrics')
 
     def vo_geometry(self, agents, pos, rA, arg, theta_ba, collided):
         """d2d_vo_geometry: agents [B, 6, N], pos [P, 2] -> arg, theta_ba [B, P, N] float64, collided [B, P] uint8"""

@@ -35,20 +35,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../../include/d2d.h" /* D2D_AF, D2D_A_*: the rows of the state's agents [6][N] */
 #include "../../../include/d2d_metrics.h"
 
 #ifndef D2D_DF_QUAL
 #define D2D_DF_QUAL static inline
 #endif
-
-/* rows of the state's agents [6][N] (include/d2d.h D2D_A_*) */
-#define D2D_DF_A_PX 0
-#define D2D_DF_A_PY 1
-#define D2D_DF_A_VX 2
-#define D2D_DF_A_VY 3
-#define D2D_DF_A_R 4
-#define D2D_DF_A_R2 5
-#define D2D_DF_AF 6
 
 #define D2D_DF_UNOCCUPIED 2
 
@@ -128,13 +120,13 @@ D2D_DF_QUAL void d2d_fit_first_hit_seq(const double *agents, const double *pos, 
                                        double *work) {
   double *px = work, *py = work + N, *vx = work + 2 * (size_t)N, *vy = work + 3 * (size_t)N, *rr = work + 4 * (size_t)N;
   for (int b = 0; b < B; ++b) {
-    const double *ag = agents + (size_t)b * D2D_DF_AF * N;
+    const double *ag = agents + (size_t)b * D2D_AF * N;
     for (int j = 0; j < N; ++j) {
-      px[j] = ag[D2D_DF_A_PX * N + j];
-      py[j] = ag[D2D_DF_A_PY * N + j];
-      vx[j] = ag[D2D_DF_A_VX * N + j];
-      vy[j] = ag[D2D_DF_A_VY * N + j];
-      rr[j] = ag[D2D_DF_A_R * N + j] + drone_radius;
+      px[j] = ag[D2D_A_PX * N + j];
+      py[j] = ag[D2D_A_PY * N + j];
+      vx[j] = ag[D2D_A_VX * N + j];
+      vy[j] = ag[D2D_A_VY * N + j];
+      rr[j] = ag[D2D_A_R * N + j] + drone_radius;
     }
     for (int p = 0; p < P; ++p) first[(size_t)b * P + p] = -1;
     for (int k = -1; k < checks; ++k) {
@@ -144,17 +136,17 @@ D2D_DF_QUAL void d2d_fit_first_hit_seq(const double *agents, const double *pos, 
           for (int j = 0; j < N && *f < 0; ++j)
             if (d2d_fit_hits(pos[2 * p], pos[2 * p + 1], px[j], py[j], rr[j])) *f = k;
         }
-      for (int j = 0; j < N; ++j) d2d_fit_agent_step(px + j, py + j, vx + j, vy + j, ag[D2D_DF_A_R * N + j], W_px, H_px, scale, dt);
+      for (int j = 0; j < N; ++j) d2d_fit_agent_step(px + j, py + j, vx + j, vy + j, ag[D2D_A_R * N + j], W_px, H_px, scale, dt);
     }
     if (agents_out) {
-      double *o = agents_out + (size_t)b * D2D_DF_AF * N;
+      double *o = agents_out + (size_t)b * D2D_AF * N;
       for (int j = 0; j < N; ++j) {
-        o[D2D_DF_A_PX * N + j] = px[j];
-        o[D2D_DF_A_PY * N + j] = py[j];
-        o[D2D_DF_A_VX * N + j] = vx[j];
-        o[D2D_DF_A_VY * N + j] = vy[j];
-        o[D2D_DF_A_R * N + j] = ag[D2D_DF_A_R * N + j];
-        o[D2D_DF_A_R2 * N + j] = ag[D2D_DF_A_R2 * N + j];
+        o[D2D_A_PX * N + j] = px[j];
+        o[D2D_A_PY * N + j] = py[j];
+        o[D2D_A_VX * N + j] = vx[j];
+        o[D2D_A_VY * N + j] = vy[j];
+        o[D2D_A_R * N + j] = ag[D2D_A_R * N + j];
+        o[D2D_A_R2 * N + j] = ag[D2D_A_R2 * N + j];
       }
     }
   }

@@ -27,6 +27,7 @@
 // Arithmetic is fp64 in the reference's own operation order (d2d_vo.h, d2d_difficulty.h), compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -56,6 +57,14 @@ int fail(int rc, const char *msg) {
   return rc;
 }
 
+__attribute__((format(printf, 2, 3))) int failf(int rc, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+  return rc;
+}
+
 __device__ __forceinline__ double readlane_f64(double v, int src) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src);
@@ -77,9 +86,9 @@ __global__ __launch_bounds__(EW_BLOCK) void vo_pairs_kernel(const double *__rest
   const int j = (int)(i % N);
   const long long bp = i / N;
   const int p = (int)(bp % P);
-  const double *ag = agents + (size_t)(bp / P) * D2D_VO_AF * N;
+  const double *ag = agents + (size_t)(bp / P) * D2D_AF * N;
   double a, t;
-  d2d_vo_pair(pos[2 * p], pos[2 * p + 1], ag[D2D_VO_A_PX * N + j], ag[D2D_VO_A_PY * N + j], rA, ag[D2D_VO_A_R * N + j], &a, &t);
+  d2d_vo_pair(pos[2 * p], pos[2 * p + 1], ag[D2D_A_PX * N + j], ag[D2D_A_PY * N + j], rA, ag[D2D_A_R * N + j], &a, &t);
   arg[i] = a;
   theta_ba[i] = t;
 }
@@ -89,10 +98,10 @@ __global__ __launch_bounds__(EW_BLOCK) void vo_collided_kernel(const double *__r
   const long long bp = (long long)blockIdx.x * EW_BLOCK + threadIdx.x;
   if (bp >= BP) return;
   const int p = (int)(bp % P);
-  const double *ag = agents + (size_t)(bp / P) * D2D_VO_AF * N;
+  const double *ag = agents + (size_t)(bp / P) * D2D_AF * N;
   const double ax = pos[2 * p], ay = pos[2 * p + 1];
   int hit = 0;
-  for (int j = 0; j < N; ++j) hit |= d2d_vo_hits(ax, ay, ag[D2D_VO_A_PX * N + j], ag[D2D_VO_A_PY * N + j], rA, ag[D2D_VO_A_R * N + j]);
+  for (int j = 0; j < N; ++j) hit |= d2d_vo_hits(ax, ay, ag[D2D_A_PX * N + j], ag[D2D_A_PY * N + j], rA, ag[D2D_A_R * N + j]);
   collided[bp] = (uint8_t)hit;
 }
 
@@ -121,7 +130,7 @@ __global__ __launch_bounds__(WAVE) void vo_count_kernel(const double *__restrict
   const int p0 = blockIdx.y * VO_PCH, b = blockIdx.z;
   const int np = min(VO_PCH, P - p0);
   const size_t bp0 = (size_t)b * P + p0;
-  const double *ag = agents + (size_t)b * D2D_VO_AF * N;
+  const double *ag = agents + (size_t)b * D2D_AF * N;
   const bool valid = c < C;
   const double cx = valid ? cand[2 * c] : 0.0, cy = valid ? cand[2 * c + 1] : 0.0;
   const unsigned long long vm = __ballot(valid);
@@ -133,7 +142,7 @@ __global__ __launch_bounds__(WAVE) void vo_count_kernel(const double *__restrict
     const int na = min(VO_TILE, N - a0);
     __syncthreads();                            // the previous tile has been read
     for (int a = 0; a < na; ++a)
-      td[a * WAVE + lane] = valid ? d2d_vo_theta_dif(cx, cy, ag[D2D_VO_A_VX * N + a0 + a], ag[D2D_VO_A_VY * N + a0 + a]) : 0.0;
+      td[a * WAVE + lane] = valid ? d2d_vo_theta_dif(cx, cy, ag[D2D_A_VX * N + a0 + a], ag[D2D_A_VY * N + a0 + a]) : 0.0;
     __syncthreads();
     for (int pi = 0; pi < np; ++pi) {
       const unsigned long long m = readlane_u64(mask, pi);
@@ -176,17 +185,17 @@ __global__ __launch_bounds__(WAVE) void fit_first_hit_kernel(const double *__res
                                                             int32_t *__restrict__ first, double *__restrict__ agents_out) {
   const int lane = threadIdx.x;
   const long long p = (long long)blockIdx.y * WAVE + lane;
-  const double *ag = agents + (size_t)blockIdx.x * D2D_DF_AF * N;
+  const double *ag = agents + (size_t)blockIdx.x * D2D_AF * N;
   double px[NT], py[NT], vx[NT], vy[NT], r[NT], rr[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int j = t * WAVE + lane;
     const bool live = j < N;                    // lanes beyond N neither load nor store
-    px[t] = live ? ag[D2D_DF_A_PX * N + j] : 0.0;
-    py[t] = live ? ag[D2D_DF_A_PY * N + j] : 0.0;
-    vx[t] = live ? ag[D2D_DF_A_VX * N + j] : 0.0;
-    vy[t] = live ? ag[D2D_DF_A_VY * N + j] : 0.0;
-    r[t] = live ? ag[D2D_DF_A_R * N + j] : 0.0;
+    px[t] = live ? ag[D2D_A_PX * N + j] : 0.0;
+    py[t] = live ? ag[D2D_A_PY * N + j] : 0.0;
+    vx[t] = live ? ag[D2D_A_VX * N + j] : 0.0;
+    vy[t] = live ? ag[D2D_A_VY * N + j] : 0.0;
+    r[t] = live ? ag[D2D_A_R * N + j] : 0.0;
     rr[t] = r[t] + drone_radius;
   }
   const bool mine = p < P;                      // lanes beyond P neither load nor store
@@ -209,40 +218,33 @@ __global__ __launch_bounds__(WAVE) void fit_first_hit_kernel(const double *__res
   }
   if (mine) first[(size_t)blockIdx.x * P + p] = f;
   if (agents_out != nullptr && blockIdx.y == 0) {
-    double *o = agents_out + (size_t)blockIdx.x * D2D_DF_AF * N;
+    double *o = agents_out + (size_t)blockIdx.x * D2D_AF * N;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int j = t * WAVE + lane;
       if (j < N) {
-        o[D2D_DF_A_PX * N + j] = px[t];
-        o[D2D_DF_A_PY * N + j] = py[t];
-        o[D2D_DF_A_VX * N + j] = vx[t];
-        o[D2D_DF_A_VY * N + j] = vy[t];
-        o[D2D_DF_A_R * N + j] = r[t];
-        o[D2D_DF_A_R2 * N + j] = ag[D2D_DF_A_R2 * N + j];
+        o[D2D_A_PX * N + j] = px[t];
+        o[D2D_A_PY * N + j] = py[t];
+        o[D2D_A_VX * N + j] = vx[t];
+        o[D2D_A_VY * N + j] = vy[t];
+        o[D2D_A_R * N + j] = r[t];
+        o[D2D_A_R2 * N + j] = ag[D2D_A_R2 * N + j];
       }
     }
   }
 }
 
 int check_sizes(const char *who, long long B, long long N, long long P, long long C) {
-  char msg[200];
-  if (B < 1 || N < 1 || P < 1 || C < 1) {
-    snprintf(msg, sizeof msg, "%s: B, N, P, C >= 1", who);
-    return fail(-1, msg);
-  }
-  if (B > D2D_VO_MAX_B || P > D2D_VO_MAX_P || B * P > D2D_VO_MAX_ELEMS / (2 * N)) {
-    snprintf(msg, sizeof msg, "%s: B <= %d, P <= %d and B * P * N * 2 <= %d", who, D2D_VO_MAX_B, D2D_VO_MAX_P, D2D_VO_MAX_ELEMS);
-    return fail(-4, msg);
-  }
+  if (B < 1 || N < 1 || P < 1 || C < 1) return failf(-1, "%s: B, N, P, C >= 1", who);
+  if (B > D2D_VO_MAX_B || P > D2D_VO_MAX_P || B * P > D2D_VO_MAX_ELEMS / (2 * N))
+    return failf(-4, "%s: B <= %d, P <= %d and B * P * N * 2 <= %d", who, D2D_VO_MAX_B, D2D_VO_MAX_P, D2D_VO_MAX_ELEMS);
   return 0;
 }
 
 int launched(const char *who) {
   const hipError_t err = hipGetLastError();
   if (err == hipSuccess) return 0;
-  snprintf(g_err, sizeof g_err, "%s: launch failed: %s", who, hipGetErrorString(err));
-  return -3;
+  return failf(-3, "%s: launch failed: %s", who, hipGetErrorString(err));
 }
 
 unsigned blocks_of(long long n) { return (unsigned)((n + EW_BLOCK - 1) / EW_BLOCK); }
@@ -307,11 +309,8 @@ int d2d_fit_first_hit(const double *agents, const double *pos, double drone_radi
                       int32_t B, int32_t N, int32_t P, int32_t checks, int32_t *first, double *agents_out, void *stream) {
   if (B < 1 || N < 1 || P < 1 || checks < 0) return fail(-1, "d2d_fit_first_hit: B, N, P >= 1 and checks >= 0");
   if (!agents || !pos || !first) return fail(-1, "d2d_fit_first_hit: a pointer is NULL");
-  if (N > D2D_FIT_MAX_N || P > D2D_FIT_MAX_P || (long long)B * P > D2D_FIT_MAX_ELEMS || (long long)B * D2D_DF_AF * N > D2D_FIT_MAX_ELEMS) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "d2d_fit_first_hit: N <= %d, P <= %d and B * max(P, 6 * N) <= %d", D2D_FIT_MAX_N, D2D_FIT_MAX_P, D2D_FIT_MAX_ELEMS);
-    return fail(-4, msg);
-  }
+  if (N > D2D_FIT_MAX_N || P > D2D_FIT_MAX_P || (long long)B * P > D2D_FIT_MAX_ELEMS || (long long)B * D2D_AF * N > D2D_FIT_MAX_ELEMS)
+    return failf(-4, "d2d_fit_first_hit: N <= %d, P <= %d and B * max(P, 6 * N) <= %d", D2D_FIT_MAX_N, D2D_FIT_MAX_P, D2D_FIT_MAX_ELEMS);
   const dim3 grid((unsigned)B, (unsigned)((P + WAVE - 1) / WAVE));
 #define FIT_LAUNCH(NT)                                                                                                                  \
   hipLaunchKernelGGL(fit_first_hit_kernel<NT>, grid, dim3(WAVE), 0, (hipStream_t)stream, agents, pos, drone_radius, W_px, H_px, scale, dt, \

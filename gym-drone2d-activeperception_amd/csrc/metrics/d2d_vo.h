@@ -27,6 +27,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../../include/d2d.h" /* D2D_AF, D2D_A_*: the rows of the state's agents [6][N] */
 #include "../../../include/d2d_metrics.h"
 
 #ifndef D2D_VO_QUAL
@@ -40,14 +41,6 @@
 #endif
 #include "../d2d_atan2.h"
 #include "../d2d_sincos.h"
-
-/* rows of the state's agents [6][N] that the metric reads (include/d2d.h D2D_A_*) */
-#define D2D_VO_A_PX 0
-#define D2D_VO_A_PY 1
-#define D2D_VO_A_VX 2
-#define D2D_VO_A_VY 3
-#define D2D_VO_A_R 4
-#define D2D_VO_AF 6
 
 /* numpy.linalg.norm of the 2-vector (x, y) */
 D2D_VO_QUAL double d2d_vo_norm(double x, double y) { return __builtin_sqrt(D2D_FMA(y, y, x * x)); }
@@ -98,12 +91,12 @@ D2D_VO_QUAL int d2d_vo_in_between(double right, double dif, double left) {
 D2D_VO_QUAL void d2d_vo_geometry_seq(const double *agents, const double *pos, double rA, int B, int N, int P, double *arg,
                                      double *theta_ba, uint8_t *collided) {
   for (int b = 0; b < B; ++b) {
-    const double *ag = agents + (size_t)b * D2D_VO_AF * N;
+    const double *ag = agents + (size_t)b * D2D_AF * N;
     for (int p = 0; p < P; ++p) {
       int hit = 0;
       for (int j = 0; j < N; ++j) {
         const size_t o = ((size_t)b * P + p) * N + j;
-        hit |= d2d_vo_pair(pos[2 * p], pos[2 * p + 1], ag[D2D_VO_A_PX * N + j], ag[D2D_VO_A_PY * N + j], rA, ag[D2D_VO_A_R * N + j],
+        hit |= d2d_vo_pair(pos[2 * p], pos[2 * p + 1], ag[D2D_A_PX * N + j], ag[D2D_A_PY * N + j], rA, ag[D2D_A_R * N + j],
                            arg + o, theta_ba + o);
       }
       collided[(size_t)b * P + p] = (uint8_t)hit;
@@ -124,7 +117,7 @@ D2D_VO_QUAL void d2d_vo_cones_seq(const double *theta_ba, const double *half, co
 D2D_VO_QUAL void d2d_vo_count_seq(const double *agents, const double *cand, const double *cone, const uint8_t *collided, int B,
                                   int N, int P, int C, int32_t *count) {
   for (int b = 0; b < B; ++b) {
-    const double *ag = agents + (size_t)b * D2D_VO_AF * N;
+    const double *ag = agents + (size_t)b * D2D_AF * N;
     for (int p = 0; p < P; ++p) {
       const size_t bp = (size_t)b * P + p;
       if (collided[bp]) {
@@ -135,7 +128,7 @@ D2D_VO_QUAL void d2d_vo_count_seq(const double *agents, const double *cand, cons
       for (int c = 0; c < C; ++c) {
         int suit = 1;
         for (int j = 0; j < N && suit; ++j) {
-          const double dif = d2d_vo_theta_dif(cand[2 * c], cand[2 * c + 1], ag[D2D_VO_A_VX * N + j], ag[D2D_VO_A_VY * N + j]);
+          const double dif = d2d_vo_theta_dif(cand[2 * c], cand[2 * c + 1], ag[D2D_A_VX * N + j], ag[D2D_A_VY * N + j]);
           if (d2d_vo_in_between(cone[2 * (bp * N + j)], dif, cone[2 * (bp * N + j) + 1])) suit = 0;
         }
         n += suit;

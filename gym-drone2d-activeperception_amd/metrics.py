@@ -31,9 +31,10 @@ import numpy as np
 import torch
 
 from . import _abi as A
+from ._lib import backend_for
 from .params import Params
 from . import sweeps
-from .sweeps import _table_order
+from .sweeps import _host_worlds, _on_device, _per_agent_count, _record, _table_order
 from .vec_env import build_worlds, build_worlds_device_of
 
 VO_SCRIPT = 'script/difficulty_calculator/vo_calculator.py'
@@ -71,14 +72,25 @@ def vo_candidates(v_min=20, v_max=60):
     return np.array(out, dtype=np.float64).reshape(-1, 2)
 
 
-def _backend_of(backend, device):
-    if backend is None:
-        from ._lib import HipBackend
-        backend = HipBackend(device)
-    if not getattr(backend, 'supports_vo_metric', False):
-        raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} has no velocity-obstacle metric '
-                                  f'(include/d2d_metrics.h): run the reference\'s {VO_SCRIPT}')
-    return backend
+def _backend_of(backend, device, script):
+    """The backend of a metric of `script` (backend_for): one with the velocity-obstacle kernels for VO_SCRIPT, with the
+    traversability / survival-fit kernels for the other two."""
+    flag, what = ('supports_vo_metric', 'velocity-obstacle') if script == VO_SCRIPT else \
+        ('supports_difficulty_tables', 'traversability / survival-fit')
+    return backend_for(backend, device, flag, f'has no {what} metric (include/d2d_metrics.h): run the reference\'s {script}')
+
+
+def _seeded_worlds(who, plist, worlds, backend, fields):
+    """The tensors `fields` ('agents', 'gt') of the seeded worlds of `plist` on the backend's device: built here on the host
+    (worlds=None), taken from a list of host worlds, or built by the device (worlds='device'; the grid in the reference's [W][H]
+    indexing whatever layout the device keeps)."""
+    dev = torch.device(backend.device)
+    if _on_device(worlds):
+        state = build_worlds_device_of(plist, backend=backend).state
+        return [state.logical(f).contiguous() for f in fields]
+    seeded = _host_worlds(who, plist, worlds)
+    dtype = dict(agents=np.float64, gt=np.uint8)
+    return [torch.from_numpy(np.stack([np.asarray(w[f], dtype=dtype[f]) for w in seeded])).to(dev) for f in fields]
 
 
 def host_asin(arg):
@@ -94,7 +106,7 @@ def vo_counts(agents, positions, cand, rA=R_A, backend=None, return_parts=False,
     on the backend's device.  Returns count [B, P] int32 (the suitable candidates; -1: the position is inside an agent's disc); with
     `return_parts` also a dict of arg, theta_ba, half [B, P, N], collided [B, P] and cone [B, P, N, 2].  `timings`: a dict that
     receives geometry_s, asin_s (D2H, asin, H2D), cones_s, count_s, each synchronised on both sides."""
-    backend = _backend_of(backend, agents.device)
+    backend = _backend_of(backend, agents.device, VO_SCRIPT)
     dev = agents.device
     agents = agents.contiguous()
     positions = positions.to(torch.float64).contiguous()
@@ -136,22 +148,14 @@ def vo_feasibility_batch(indices, position_step=30, device='cuda:0', backend=Non
     'device' (built by the device, vec_env.build_worlds_device_of).
     `timings`: a dict that collects, per call, build_s, geometry_s, asin_s, cones_s, count_s and post_s (each synchronised on both
     sides) under 'batches', and their totals."""
-    backend = _backend_of(backend, device)
+    backend = _backend_of(backend, device, VO_SCRIPT)
     t_build = time.perf_counter()
     plist = [_params(ix) for ix in indices]
     xs, ys = vo_positions(plist[0], position_step)
     pos = np.array([(x, y) for x in xs for y in ys], dtype=np.float64).reshape(-1, 2)
     cand = vo_candidates()
-    dev = torch.device(backend.device)
-    if isinstance(worlds, str):
-        if worlds != 'device':
-            raise ValueError(f"worlds {worlds!r}: a list of host worlds or 'device'")
-        agents = build_worlds_device_of(plist, backend=backend).state.t['agents']
-    else:
-        seeded = worlds if worlds is not None else [build_worlds(p, 1)[0] for p in plist]
-        if len(seeded) != len(plist):
-            raise ValueError(f'vo_feasibility_batch: {len(seeded)} worlds for {len(plist)} settings')
-        agents = torch.from_numpy(np.stack([np.asarray(w['agents'], dtype=np.float64) for w in seeded])).to(dev)
+    agents, = _seeded_worlds('vo_feasibility_batch', plist, worlds, backend, ('agents',))
+    dev = agents.device
     if timings is not None:
         backend.sync()
     rec = {} if timings is not None else None
@@ -164,9 +168,7 @@ def vo_feasibility_batch(indices, position_step=30, device='cuda:0', backend=Non
     if timings is not None:
         rec.update(N=int(agents.shape[2]), worlds=len(plist), positions=len(pos), candidates=C, build_s=t_dev - t_build,
                    post_s=time.perf_counter() - t_post)
-        timings.setdefault('batches', []).append(rec)
-        for k in ('build_s', 'geometry_s', 'asin_s', 'cones_s', 'count_s', 'post_s', 'worlds'):
-            timings[k] = timings.get(k, 0) + rec[k]
+        _record(timings, rec, ('build_s', 'geometry_s', 'asin_s', 'cones_s', 'count_s', 'post_s', 'worlds'))
     return rates
 
 
@@ -175,13 +177,12 @@ def vo_feasibility(index, position_step=30, device='cuda:0', backend=None, world
     return np.mean(vo_feasibility_batch([index], position_step, device, backend, worlds)[0])
 
 
-def _by_agent_number(order, agent_numbers, fn):
-    result = [None] * len(order)
-    for n in dict.fromkeys(agent_numbers):       # one batch per agent count (a batch shares N)
-        sel = [i for i, ix in enumerate(order) if ix['agent_number'] == n]
-        for i, g in zip(sel, fn(sel)):
-            result[i] = g
-    return result
+def _table(who, order, map_ids, agent_numbers, worlds, batch):
+    """The nested list of a difficulty table: one batch(indices, their worlds) per agent count (sweeps._per_agent_count), its
+    metrics put back in the order of `order` and cut into one row per map_id."""
+    flat = _per_agent_count(who, order, agent_numbers, worlds, batch)
+    per_map = len(order) // max(len(map_ids), 1)
+    return [flat[m * per_map:(m + 1) * per_map] for m in range(len(map_ids))]
 
 
 def vo_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_sizes=(5, 10, 15), agent_speeds=(20, 40, 60), position_step=30,
@@ -190,15 +191,10 @@ def vo_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_sizes=(5, 10, 
     product(agent_num, agent_size, agent_vel) metrics.  `worlds`: None, 'device', or one host world per setting in that order."""
     map_ids = list(map_ids)
     order = _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds)
-    if worlds is not None and not isinstance(worlds, str) and len(worlds) != len(order):
-        raise ValueError(f'vo_table: {len(worlds)} worlds for {len(order)} settings')
 
-    def batch(sel):
-        w = worlds if worlds is None or isinstance(worlds, str) else [worlds[i] for i in sel]
-        return [np.mean(r) for r in vo_feasibility_batch([order[i] for i in sel], position_step, device, backend, w, timings)]
-    flat = _by_agent_number(order, agent_numbers, batch)
-    per_map = len(order) // max(len(map_ids), 1)
-    return [flat[m * per_map:(m + 1) * per_map] for m in range(len(map_ids))]
+    def batch(indices, w):
+        return [np.mean(r) for r in vo_feasibility_batch(indices, position_step, device, backend, w, timings)]
+    return _table('vo_table', order, map_ids, agent_numbers, worlds, batch)
 
 
 def density(index, world=None):
@@ -221,54 +217,20 @@ def density_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_sizes=(5,
     """The nested list behind density.csv (density_calculator.py:33-51), in the same order as vo_table."""
     map_ids = list(map_ids)
     order = _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds)
-    if worlds is not None and len(worlds) != len(order):
-        raise ValueError(f'density_table: {len(worlds)} worlds for {len(order)} settings')
-    flat = [density(ix, None if worlds is None else worlds[i]) for i, ix in enumerate(order)]
-    per_map = len(order) // max(len(map_ids), 1)
-    return [flat[m * per_map:(m + 1) * per_map] for m in range(len(map_ids))]
+
+    def batch(indices, w):
+        return [density(ix, None if w is None else w[k]) for k, ix in enumerate(indices)]
+    return _table('density_table', order, map_ids, agent_numbers, worlds, batch)
 
 
 # ---- traversibility_calculator.py and survivability_calculator.py
-
-def _tables_backend_of(backend, device, script):
-    if backend is None:
-        from ._lib import HipBackend
-        backend = HipBackend(device)
-    if not getattr(backend, 'supports_difficulty_tables', False):
-        raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} has no traversability / survival-fit metric '
-                                  f'(include/d2d_metrics.h): run the reference\'s {script}')
-    return backend
-
-
-def _seeded_worlds(who, plist, worlds, backend, fields):
-    """The tensors `fields` ('agents', 'gt') of the seeded worlds of `plist` on the backend's device: built here on the host
-    (worlds=None), taken from a list of host worlds, or built by the device (worlds='device'; the grid in the reference's [W][H]
-    indexing whatever layout the device keeps)."""
-    dev = torch.device(backend.device)
-    if isinstance(worlds, str):
-        if worlds != 'device':
-            raise ValueError(f"worlds {worlds!r}: a list of host worlds or 'device'")
-        state = build_worlds_device_of(plist, backend=backend).state
-        return [state.logical(f).contiguous() for f in fields]
-    seeded = worlds if worlds is not None else [build_worlds(p, 1)[0] for p in plist]
-    if len(seeded) != len(plist):
-        raise ValueError(f'{who}: {len(seeded)} worlds for {len(plist)} settings')
-    dtype = dict(agents=np.float64, gt=np.uint8)
-    return [torch.from_numpy(np.stack([np.asarray(w[f], dtype=dtype[f]) for w in seeded])).to(dev) for f in fields]
-
-
-def _record(timings, rec, keys):
-    timings.setdefault('batches', []).append(rec)
-    for k in keys:
-        timings[k] = timings.get(k, 0) + rec[k]
-
 
 def trav_steps(gt, starts, backend=None):
     """One launch of d2d_trav_steps.  gt [B, W, H] uint8 on the backend's device, in the reference's indexing; starts: S pairs
     (i, j) of host integers.  Returns steps [B, S, 8] int32 on the device: the steps walked towards N, NE, E, SE, S, SW, W, NW, or
     -1 in all eight where the start cell is not UNOCCUPIED.  A start outside the grid is refused here, before it is uploaded: the
     library cannot look into device memory before its launch."""
-    backend = _tables_backend_of(backend, gt.device, TRAV_SCRIPT)
+    backend = _backend_of(backend, gt.device, TRAV_SCRIPT)
     st = np.asarray(starts, dtype=np.int64).reshape(-1, 2)
     if gt.dim() != 3 or gt.dtype != torch.uint8 or len(st) < 1:
         raise ValueError('trav_steps: gt [B, W, H] uint8, starts [S, 2] with S >= 1')
@@ -316,7 +278,7 @@ def traversibility_batch(indices, axis_range=TRAV_AXIS, device='cuda:0', backend
     the reference's gym-metric-v1 env builds for these parameters.  `worlds`: as in vo_feasibility_batch.
     `timings`: a dict that collects, per call, build_s, launch_s, d2h_s and post_s (each synchronised on both sides) under
     'batches', and their totals."""
-    backend = _tables_backend_of(backend, device, TRAV_SCRIPT)
+    backend = _backend_of(backend, device, TRAV_SCRIPT)
     t0 = time.perf_counter()
     for ix in indices:
         if ix['agent_size'] == -1:
@@ -353,15 +315,10 @@ def traversibility_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_si
     per map_id, each with product(agent_num, agent_size, agent_vel) metrics.  `worlds`: as in vo_table."""
     map_ids = list(map_ids)
     order = _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds)
-    if worlds is not None and not isinstance(worlds, str) and len(worlds) != len(order):
-        raise ValueError(f'traversibility_table: {len(worlds)} worlds for {len(order)} settings')
 
-    def batch(sel):
-        w = worlds if worlds is None or isinstance(worlds, str) else [worlds[i] for i in sel]
-        return [trav_metric(v) for v in traversibility_batch([order[i] for i in sel], axis_range, device, backend, w, timings)]
-    flat = _by_agent_number(order, agent_numbers, batch)
-    per_map = len(order) // max(len(map_ids), 1)
-    return [flat[m * per_map:(m + 1) * per_map] for m in range(len(map_ids))]
+    def batch(indices, w):
+        return [trav_metric(v) for v in traversibility_batch(indices, axis_range, device, backend, w, timings)]
+    return _table('traversibility_table', order, map_ids, agent_numbers, worlds, batch)
 
 
 def fit_first_hit(agents, positions, params, checks, backend=None, return_agents=False):
@@ -369,7 +326,7 @@ def fit_first_hit(agents, positions, params, checks, backend=None, return_agents
     backend's device; params: map_size, map_scale, dt and drone_radius of the worlds.  Returns first [B, P] int32 (the index of the
     first of `checks` checks in which an agent touched the drone standing there, -1: none did); with `return_agents` also the agents
     after the checks + 1 updates."""
-    backend = _tables_backend_of(backend, agents.device, FIT_SCRIPT)
+    backend = _backend_of(backend, agents.device, FIT_SCRIPT)
     agents = agents.contiguous()
     positions = positions.to(torch.float64).contiguous()
     if agents.dim() != 3 or agents.shape[1] != A.AF or agents.dtype != torch.float64 or positions.dim() != 2 or positions.shape[1] != 2:
@@ -404,7 +361,7 @@ def survival_fit_batch(indices, position_step=60, T=12, device='cuda:0', backend
     `worlds`: None (built here on the host), a list of host worlds of `indices` built with sweeps._params(index), or 'device'.
     `timings`: as in traversibility_batch.  `return_agents`: also the agents [len(indices), 6, N] (a device tensor) as the
     reference's env holds them when env_metrics returns."""
-    backend = _tables_backend_of(backend, device, FIT_SCRIPT)
+    backend = _backend_of(backend, device, FIT_SCRIPT)
     t0 = time.perf_counter()
     for ix in indices:
         if ix.get('motion_profile', 'CVM') != 'CVM':
@@ -446,12 +403,7 @@ def survival_fit_table(map_ids=(0,), agent_numbers=range(10, 30, 2), agent_sizes
     `worlds`: None, 'device', or one host world per setting in that order."""
     map_ids, agent_numbers = list(map_ids), list(agent_numbers)
     order = _table_order(map_ids, agent_numbers, list(agent_sizes), list(agent_speeds))
-    if worlds is not None and not isinstance(worlds, str) and len(worlds) != len(order):
-        raise ValueError(f'survival_fit_table: {len(worlds)} worlds for {len(order)} settings')
 
-    def batch(sel):
-        w = worlds if worlds is None or isinstance(worlds, str) else [worlds[i] for i in sel]
-        return [np.mean(t) for t in survival_fit_batch([order[i] for i in sel], position_step, T, device, backend, w, timings)]
-    flat = _by_agent_number(order, agent_numbers, batch)
-    per_map = len(order) // max(len(map_ids), 1)
-    return [flat[m * per_map:(m + 1) * per_map] for m in range(len(map_ids))]
+    def batch(indices, w):
+        return [np.mean(t) for t in survival_fit_batch(indices, position_step, T, device, backend, w, timings)]
+    return _table('survival_fit_table', order, map_ids, agent_numbers, worlds, batch)

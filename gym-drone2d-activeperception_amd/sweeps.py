@@ -14,6 +14,7 @@ import itertools
 import numpy as np
 import torch
 
+from ._lib import backend_for
 from .params import Params
 from .vec_env import VecDrone2DEnv, build_worlds, build_worlds_device_of, build_worlds_of
 
@@ -35,6 +36,28 @@ def start_cells(params, position_step=60):
     return xs, ys
 
 
+def _on_device(worlds):
+    """Is `worlds` 'device' (the seeded worlds are built by the device)?  Any other string is refused."""
+    if isinstance(worlds, str) and worlds != 'device':
+        raise ValueError(f"worlds {worlds!r}: a list of host worlds or 'device'")
+    return isinstance(worlds, str)
+
+
+def _host_worlds(who, plist, worlds):
+    """The seeded host worlds of `plist`: the caller's list, one each, or built here (worlds=None)."""
+    seeded = worlds if worlds is not None else [build_worlds(p, 1)[0] for p in plist]
+    if len(seeded) != len(plist):
+        raise ValueError(f'{who}: {len(seeded)} worlds for {len(plist)} settings')
+    return seeded
+
+
+def _record(timings, rec, keys):
+    """Append the batch's record to timings['batches'] and add its `keys` to the totals."""
+    timings.setdefault('batches', []).append(rec)
+    for k in keys:
+        timings[k] = timings.get(k, 0) + rec[k]
+
+
 def survivability_batch(indices, position_step=60, T=24, device='cuda:0', backend=None, timings=None, streams=None, worlds=None):
     """Collision states of several settings that share agent_number (same N), one launch.
     Returns float64 [len(indices), len(x_range), len(y_range), n_steps] with 1 where the drone pinned at that
@@ -50,17 +73,13 @@ def survivability_batch(indices, position_step=60, T=24, device='cuda:0', backen
     xs, ys = start_cells(plist[0], position_step)
     cells = [(x, y) for x in xs for y in ys]
     n_steps = len(np.arange(0, T, 0.1))
-    if isinstance(worlds, str):
-        if worlds != 'device':
-            raise ValueError(f"worlds {worlds!r}: a list of host worlds or 'device'")
-        if backend is None:
-            from ._lib import HipBackend
-            backend = HipBackend(device)
+    if _on_device(worlds):
+        backend = backend_for(backend, device)
         pins = cells * len(plist)
         worlds = build_worlds_device_of(plist, backend=backend).spread(np.repeat(np.arange(len(plist)), len(cells)))
         worlds_n = len(pins)
     else:
-        seeded = worlds if worlds is not None else [build_worlds(p, 1)[0] for p in plist]
+        seeded = _host_worlds('survivability_batch', plist, worlds)
         worlds, pins = [], []
         for w in seeded:
             worlds += [w] * len(cells)             # every start cell begins from the same seeded world (env.reset())
@@ -88,9 +107,7 @@ def survivability_batch(indices, position_step=60, T=24, device='cuda:0', backen
     if timings is not None:
         rec = dict(N=int(env.cfg.N), envs=len(worlds), steps=n_steps, streams=ns, build_s=t_dev - t_build, device_s=t_post - t_dev,
                    post_s=time.perf_counter() - t_post, env_steps=len(worlds) * n_steps, launches=n_steps * ns)
-        timings.setdefault('batches', []).append(rec)
-        for k in ('build_s', 'device_s', 'post_s', 'env_steps', 'launches'):
-            timings[k] = timings.get(k, 0) + rec[k]
+        _record(timings, rec, ('build_s', 'device_s', 'post_s', 'env_steps', 'launches'))
         timings['last_env'] = env        # (bench.py reads the configuration and the cells per agent of the last batch)
     return out
 
@@ -103,6 +120,20 @@ def survivability(index, position_step=60, T=24, device='cuda:0', backend=None):
 def _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds):
     return [dict(motion_profile='CVM', pillar_number=0, agent_number=n, agent_speed=v, agent_size=r, map_id=m)
             for m in map_ids for (n, r, v) in itertools.product(agent_numbers, agent_sizes, agent_speeds)]
+
+
+def _per_agent_count(who, order, agent_numbers, worlds, batch):
+    """batch(indices, their worlds) for the settings of `order` with each agent count in turn (a batch shares N); the results in
+    the order of `order`.  `worlds`: None, 'device', or one host world per setting of `order`."""
+    if worlds is not None and not isinstance(worlds, str) and len(worlds) != len(order):
+        raise ValueError(f'{who}: {len(worlds)} worlds for {len(order)} settings')
+    result = [None] * len(order)
+    for n in dict.fromkeys(agent_numbers):
+        sel = [i for i, ix in enumerate(order) if ix['agent_number'] == n]
+        w = worlds if worlds is None or isinstance(worlds, str) else [worlds[i] for i in sel]
+        for i, g in zip(sel, batch([order[i] for i in sel], w)):
+            result[i] = g
+    return result
 
 
 def survivability_worlds(map_ids=range(20), agent_numbers=(10, 20, 30), agent_sizes=(5, 10, 15), agent_speeds=(20, 40, 60), workers=0):
@@ -119,13 +150,7 @@ def survivability_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_siz
     loop order: map_id outermost, then product(agent_num, agent_size, agent_vel).  `worlds`: survivability_worlds() of the same
     arguments (else the worlds are built here, one after the other), or 'device' (built by the device, one launch per agent count)."""
     order = _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds)
-    if worlds is not None and not isinstance(worlds, str) and len(worlds) != len(order):
-        raise ValueError(f'survivability_table: {len(worlds)} worlds for {len(order)} settings')
-    result = [None] * len(order)
-    for n in agent_numbers:                    # one batch per agent count (a batch shares N)
-        sel = [i for i, ix in enumerate(order) if ix['agent_number'] == n]
-        got = survivability_batch([order[i] for i in sel], position_step, T, device, backend, timings, streams,
-                                  worlds=worlds if worlds is None or isinstance(worlds, str) else [worlds[i] for i in sel])
-        for i, g in zip(sel, got):
-            result[i] = g
-    return np.array(result)
+
+    def batch(indices, w):
+        return survivability_batch(indices, position_step, T, device, backend, timings, streams, worlds=w)
+    return np.array(_per_agent_count('survivability_table', order, agent_numbers, worlds, batch))

@@ -20,6 +20,7 @@ import torch
 
 from . import _abi as A
 from . import host_init
+from ._lib import D2DError, backend_for        # (importing _lib loads no library: HipBackend() does)
 from .params import with_defaults
 from .state import BatchState
 
@@ -142,12 +143,15 @@ class DeviceWorlds:
         return out
 
 
+def _needs_device_worlds(backend):
+    backend_for(backend, None, 'supports_device_worlds',
+                'has no device world construction: build the worlds on the host (build_worlds / build_worlds_of)')
+
+
 def _build_into(backend, inp, state, check=True):
     """Run the device construction of world_inputs() `inp` into BatchState `state` (B = inp['U']); returns the host copies of
     (tracker_radius, obstacles, status).  Reading them back is the call's only synchronisation."""
-    if not getattr(backend, 'supports_device_worlds', False):
-        raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} has no device world construction: build the '
-                                  'worlds on the host (build_worlds / build_worlds_of)')
+    _needs_device_worlds(backend)
     dev = state.device
     up = {n: torch.from_numpy(inp[n].view(np.int32) if n == 'map_id' else inp[n]).to(dev) for n in ('unit', 'cells', 'map_id', 'env_par', 'env_tgt')}
     U, N, P = inp['U'], inp['N'], inp['P']
@@ -161,7 +165,6 @@ def _build_into(backend, inp, state, check=True):
     status = up['status'].cpu().numpy()
     if check and status.any():
         bad = np.nonzero(status)[0]
-        from ._lib import D2DError
         raise D2DError(f'device worlds: env {int(bad[0])} (map_id {inp["map_ids"][int(bad[0])]}) could not place its pillars and agents '
                        f'within max_attempts = {inp["max_attempts"]} ({len(bad)} of {U} envs); the reference would loop for ever')
     return up['tracker_radius'].cpu(), up['obstacles'].cpu().numpy().astype(np.int64), status
@@ -172,9 +175,7 @@ def build_worlds_device_of(params_list, device='cuda:0', backend=None, grid_layo
     """build_worlds_of on the device: one world per Params of the list, built by one launch and left resident (DeviceWorlds).
     `index`: env -> position in the list, for batches that start many envs from one world.  `check=False` returns instead of raising
     D2DError when an env hit `max_attempts` (DeviceWorlds.status says which; their fields are 0).  `map_ids`: as in world_inputs."""
-    if backend is None:
-        from ._lib import HipBackend
-        backend = HipBackend(device)
+    backend = backend_for(backend, device)
     inp = world_inputs(params_list, max_attempts, map_ids)
     p0 = with_defaults(params_list[0])
     cfg = host_init.derive_cfg(p0, B=inp['U'], N=inp['N'], T=inp['T'], grid_tile=_grid_tile(p0, backend, grid_layout))
@@ -215,10 +216,7 @@ class VecDrone2DEnv:
         self.env_offset = int(env_offset)
         planner = planner if planner is not None else self.params.planner
         self.planner_mode = A.PLANNER_NOMOVE if planner == 'NoMove' else A.PLANNER_EXTERNAL
-        if backend is None:
-            from ._lib import HipBackend       # raises if the HIP library or the GPU is missing
-            backend = HipBackend(device)
-        self.backend = backend
+        self.backend = backend = backend_for(backend, device)
         self.device = torch.device(backend.device)
         # worlds='device' / a DeviceWorlds: the seeded worlds are built by the device (include/d2d_worlds.h) and never exist on the host;
         # N and T follow from the parameters and the static map
@@ -226,10 +224,8 @@ class VecDrone2DEnv:
         on_device = dw is not None or (isinstance(worlds, str) and worlds == 'device')
         if isinstance(worlds, str) and not on_device:
             raise ValueError(f"worlds {worlds!r}: a list of host worlds, a DeviceWorlds or 'device'")
-        if on_device and not getattr(backend, 'supports_device_worlds', False):
-            raise NotImplementedError(f'{getattr(backend, "name", type(backend).__name__)} has no device world construction: build '
-                                      'the worlds on the host (build_worlds / build_worlds_of)')
         if on_device:
+            _needs_device_worlds(backend)
             inp = None if dw is not None else world_inputs([self.params], map_ids=_seeded(self.params, self.num_envs, self.env_offset))
             N, T = (dw.N, dw.T) if dw is not None else (inp['N'], inp['T'])
             if dw is not None and dw.num_envs != self.num_envs:

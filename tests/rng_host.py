@@ -1,31 +1,24 @@
 """Host build of csrc/d2d_rng.h (tests/csrc/rng_host.c) and the numpy side of the comparisons: shared by test_rng_cpu.py and the
 GPU tests of the device noise stream."""
 import ctypes as C
-import os
 import platform
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_tan import _cpu_has_fma
+import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RNG_WORDS, RNG_POS, RNG_NPAIR, RNG_NREGEN = 640, 624, 625, 626
 
 # the stream calls libm's log through csrc/d2d_log.h: the same two conditions as tests/test_log.py
 needs_glibc_235 = pytest.mark.skipif(platform.libc_ver()[0] != 'glibc' or platform.libc_ver()[1] != '2.35',
                                      reason=f'd2d_log.h restates the log of glibc 2.35; this host has {platform.libc_ver()}')
-needs_fma = pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA log variant on this CPU')
+needs_fma = host_build.needs_fma('libm dispatches a non-FMA log variant on this CPU')
 
 
 def build_rng_host(tmpdir):
     """draw(state uint32[640], m) -> float64 [m, 2]; advances `state` in place"""
-    so = os.path.join(str(tmpdir), 'librnghost.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'rng_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('rng_host.c', tmpdir, 'librnghost.so')
     lib.d2d_rng_host_draw.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.d2d_rng_host_draw.restype = C.c_int
 

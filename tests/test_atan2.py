@@ -3,25 +3,18 @@ special cases over libm's atan2) bit for bit.  test_gpu_heading_gaze.py checks t
 libm through a C helper and from math.atan2, never from np.arctan2 (numpy may dispatch its own vectorised atan2)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from test_tan import _cpu_has_fma
+import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
 def atan2_host(tmp_path_factory):
     """(restatement, libm) as numpy functions of (y, x)"""
-    so = str(tmp_path_factory.mktemp('atan2') / 'libatan2host.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'atan2_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('atan2_host.c', tmp_path_factory.mktemp('atan2'), 'libatan2host.so')
 
     def wrap(f):
         f.argtypes = [C.c_void_p] * 3 + [C.c_int64]
@@ -76,7 +69,7 @@ def same_bits(a, b):
     return (np.isnan(a) & np.isnan(b)) | (a.view(np.int64) == b.view(np.int64))
 
 
-@pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA atan2 variant on this CPU')
+@host_build.needs_fma('libm dispatches a non-FMA atan2 variant on this CPU')
 def test_atan2_restatement_is_bit_identical_to_libm(atan2_host):
     mine, libm = atan2_host
     y, x = atan2_pairs()

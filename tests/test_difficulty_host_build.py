@@ -12,19 +12,15 @@ import difficulty_cases as DC
 import difficulty_model as M
 from drone2d_amd import _abi as A
 from drone2d_amd import sweeps
-from test_tan import _cpu_has_fma
+import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc', 'metrics')
-FLAGS = ['-O2', '-ffp-contract=off', '-mfma']
-needs_fma = pytest.mark.skipif(not _cpu_has_fma(), reason='numpy takes non-FMA norm / matmul variants on this CPU')
+CSRC = os.path.join(host_build.CSRC, 'metrics')
+needs_fma = host_build.needs_fma('numpy takes non-FMA norm / matmul variants on this CPU')
 
 
 @pytest.fixture(scope='module')
 def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp('difficulty') / 'libdifficultyhost.so')
-    subprocess.check_call(['gcc'] + FLAGS + ['-fPIC', '-shared', '-I', CSRC, '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'difficulty_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('difficulty_host.c', tmp_path_factory.mktemp('difficulty'), 'libdifficultyhost.so', include=CSRC)
     V, I, D = C.c_void_p, C.c_int32, C.c_double
     lib.difficulty_host_trav_steps.argtypes = [V, I, I, I, V, I, V]
     lib.difficulty_host_fit_first_hit.argtypes = [V, V, D, D, D, D, D, I, I, I, I, V, V, V]
@@ -94,10 +90,7 @@ def test_header_version_is_the_binding_s(host):
 def test_host_loops_run_clean_under_asan_and_ubsan(tmp_path):
     """a stand-alone program (nothing is loaded into this process; the sanitizers' runtimes are linked into it): exactly sized heap
     arrays, the 7 x 5 grid and the adversarial world whole and cut down to S = 1, P = 1, N = 1, no check and no agents_out"""
-    exe = str(tmp_path / 'difficulty_host_main')
-    subprocess.check_call(['gcc'] + FLAGS + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-static-libasan', '-static-libubsan', '-I', CSRC,
-                                            '-o', exe, os.path.join(ROOT, 'tests', 'csrc', 'difficulty_host_main.c'),
-                                            os.path.join(ROOT, 'tests', 'csrc', 'difficulty_host.c'), '-lm'])
+    exe = host_build.sanitized(['difficulty_host_main.c', 'difficulty_host.c'], tmp_path, 'difficulty_host_main', include=CSRC)
     grid, steps = DC.small_grid(), DC.grid_model('small')
     ag, m = DC.adversarial_fit_model(70, P=65)
     pos = DC.fit_positions(65)

@@ -14,12 +14,12 @@ from replay import load
 from test_atan2 import atan2_host, atan2_pairs, same_bits  # noqa: F401  (atan2_host: fixture)
 from test_gpu_plugins import _assert_same
 from test_gpu_vs_oracle import CFG5, _worlds
-from test_tan import _cpu_has_fma
+import host_build
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA atan2 variant on this CPU')
+@host_build.needs_fma('libm dispatches a non-FMA atan2 variant on this CPU')
 def test_device_atan2_is_bit_identical_to_libm(hip, atan2_host):
     y, x = atan2_pairs(seed=19)
     want = atan2_host[1](y, x)

@@ -2,31 +2,23 @@
 -m gpu the device build (d2d_log_array) against the host build on the same arguments."""
 import ctypes as C
 import math
-import os
 import platform
-import subprocess
 
 import numpy as np
 import pytest
 
 from test_atan2 import same_bits
-from test_tan import _cpu_has_fma
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 
 needs_glibc_235 = pytest.mark.skipif(platform.libc_ver()[0] != 'glibc' or platform.libc_ver()[1] != '2.35',
                                      reason=f'd2d_log.h restates the log of glibc 2.35; this host has {platform.libc_ver()}')
-needs_fma = pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA log variant on this CPU')
+needs_fma = host_build.needs_fma('libm dispatches a non-FMA log variant on this CPU')
 
 
 @pytest.fixture(scope='module')
 def log_host(tmp_path_factory):
     """(restatement, libm) as numpy functions of x"""
-    so = str(tmp_path_factory.mktemp('log') / 'libloghost.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fno-builtin', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'log_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('log_host.c', tmp_path_factory.mktemp('log'), 'libloghost.so', extra=['-fno-builtin'])
 
     def wrap(f):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]

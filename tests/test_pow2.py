@@ -2,31 +2,23 @@
 device build (d2d_pow2_array) against the host build on the same arguments.  Expected values come from libm through a C helper,
 never from numpy's `**` on arrays (numpy squares arrays with a multiplication)."""
 import ctypes as C
-import os
 import platform
-import subprocess
 
 import numpy as np
 import pytest
 
 from test_atan2 import same_bits
-from test_tan import _cpu_has_fma
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 
 needs_glibc_235 = pytest.mark.skipif(platform.libc_ver()[0] != 'glibc' or platform.libc_ver()[1] != '2.35',
                                      reason=f'd2d_pow2.h restates the pow of glibc 2.35; this host has {platform.libc_ver()}')
-needs_fma = pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA pow variant on this CPU')
+needs_fma = host_build.needs_fma('libm dispatches a non-FMA pow variant on this CPU')
 
 
 @pytest.fixture(scope='module')
 def pow2_host(tmp_path_factory):
     """(restatement, libm) as numpy functions of x"""
-    so = str(tmp_path_factory.mktemp('pow2') / 'libpow2host.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'pow2_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('pow2_host.c', tmp_path_factory.mktemp('pow2'), 'libpow2host.so')
 
     def wrap(f):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]

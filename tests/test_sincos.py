@@ -3,22 +3,17 @@ reference's math.sin / math.cos resolve to (yaw_planner.py:71): bit for bit.  Th
 test_gpu_plugins.py."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
+
 
 
 @pytest.fixture(scope='module')
 def sc_host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp('sincos') / 'libschost.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'sincos_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('sincos_host.c', tmp_path_factory.mktemp('sincos'), 'libschost.so')
     out = {}
     for name in ('sin', 'cos', 'sin1', 'cos1'):
         fn = getattr(lib, f'd2d_{name}_host_array')
@@ -31,13 +26,6 @@ def sc_host(tmp_path_factory):
             return o
         out[name] = f
     return out
-
-
-def _cpu_has_fma():
-    try:
-        return ' fma ' in open('/proc/cpuinfo').read()
-    except OSError:
-        return True
 
 
 def sincos_arguments(rng):
@@ -60,7 +48,7 @@ def sincos_arguments(rng):
     return np.concatenate(xs)
 
 
-@pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA sin / cos variant on this CPU')
+@host_build.needs_fma('libm dispatches a non-FMA sin / cos variant on this CPU')
 def test_sincos_restatement_is_bit_identical_to_libm(sc_host):
     rng = np.random.RandomState(5)
     x = sincos_arguments(rng)

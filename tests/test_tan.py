@@ -2,22 +2,16 @@
 reference's math.tan resolves to: bit for bit.  The device build is checked in test_gpu_parity.py."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_build
 
 
 @pytest.fixture(scope='module')
 def tan_host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp('tan') / 'libtanhost.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'tan_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('tan_host.c', tmp_path_factory.mktemp('tan'), 'libtanhost.so')
     lib.d2d_tan_host_array.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
 
     def f(x):
@@ -28,14 +22,7 @@ def tan_host(tmp_path_factory):
     return f
 
 
-def _cpu_has_fma():
-    try:
-        return ' fma ' in open('/proc/cpuinfo').read()
-    except OSError:
-        return True
-
-
-@pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches a non-FMA tan variant on this CPU')
+@host_build.needs_fma('libm dispatches a non-FMA tan variant on this CPU')
 def test_tan_restatement_is_bit_identical_to_libm(tan_host):
     rng = np.random.RandomState(11)
     xs = [rng.uniform(0, 2 * np.pi, 3_000_000), rng.uniform(-25, 25, 1_500_000), rng.uniform(-0.8, 0.8, 1_000_000),

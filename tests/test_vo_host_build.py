@@ -11,19 +11,15 @@ import pytest
 import vo_cases
 from drone2d_amd import _abi as A
 from drone2d_amd import metrics
-from test_tan import _cpu_has_fma
+import host_build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc', 'metrics')
-FLAGS = ['-O2', '-ffp-contract=off', '-mfma']
-needs_fma = pytest.mark.skipif(not _cpu_has_fma(), reason='libm dispatches non-FMA sin / cos / atan2 variants on this CPU')
+CSRC = os.path.join(host_build.CSRC, 'metrics')
+needs_fma = host_build.needs_fma('libm dispatches non-FMA sin / cos / atan2 variants on this CPU')
 
 
 @pytest.fixture(scope='module')
 def vo_host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp('vo') / 'libvohost.so')
-    subprocess.check_call(['gcc'] + FLAGS + ['-fPIC', '-shared', '-I', CSRC, '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'vo_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('vo_host.c', tmp_path_factory.mktemp('vo'), 'libvohost.so', include=CSRC)
     V, I = C.c_void_p, C.c_int32
     lib.vo_host_geometry.argtypes = [V, V, C.c_double, I, I, I, V, V, V]
     lib.vo_host_cones.argtypes = [V, V, V, I, I, I, V]
@@ -89,10 +85,7 @@ def test_header_version_is_the_binding_s(vo_host):
 def test_host_loops_run_clean_under_asan_and_ubsan(tmp_path):
     """a stand-alone program (nothing is loaded into this process; the sanitizers' runtimes are linked into it): exactly sized heap
     arrays, the adversarial world whole and cut down to C = 1, C = 65, P = 1 and N = 1"""
-    exe = str(tmp_path / 'vo_host_main')
-    subprocess.check_call(['gcc'] + FLAGS + ['-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-static-libasan', '-static-libubsan', '-I', CSRC, '-o', exe,
-                                            os.path.join(ROOT, 'tests', 'csrc', 'vo_host_main.c'),
-                                            os.path.join(ROOT, 'tests', 'csrc', 'vo_host.c'), '-lm'])
+    exe = host_build.sanitized(['vo_host_main.c', 'vo_host.c'], tmp_path, 'vo_host_main', include=CSRC)
     ag, cand, want = vo_cases.adversarial(), vo_cases.candidates(), vo_cases.adversarial_model()
     case = tmp_path / 'case.bin'
     with open(case, 'wb') as f:

@@ -3,9 +3,10 @@ form) and test_gpu_device_worlds.py (the kernel): every case is a list of Params
 array_equal against host_init.init_world for the same Params -- no tolerance anywhere."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -108,11 +109,7 @@ def assert_capped(got):
 def build_world_host(tmpdir):
     """gcc build of tests/csrc/world_host.c; returns (lib, run) with run(pkg, plist, grid_tile=0, max_attempts=None, rng=False) ->
     dict of numpy fields"""
-    so = os.path.join(str(tmpdir), 'libworldhost.so')
-    subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-mfma', '-fPIC', '-shared',
-                           '-I', os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc'),
-                           '-o', so, os.path.join(ROOT, 'tests', 'csrc', 'world_host.c'), '-lm'])
-    lib = C.CDLL(so)
+    lib = host_build.shared('world_host.c', tmpdir, 'libworldhost.so')
     lib.d2d_worlds_host_build.argtypes = [C.c_void_p, C.c_void_p]
     lib.d2d_worlds_host_build.restype = C.c_int
     lib.d2d_worlds_host_python.argtypes = [C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
