@@ -160,7 +160,9 @@ def bind_metrics(lib):
     sig = {
         'vo_geometry': (C.c_int, [V, V, C.c_double, I, I, I, V, V, V, V]),
         'vo_cones': (C.c_int, [V, V, V, I, I, I, V, V]),
+        'vo_cones_arg': (C.c_int, [V, V, V, I, I, I, V, V, V]),
         'vo_count': (C.c_int, [V, V, V, V, I, I, I, I, V, V]),
+        'asin_array': (C.c_int, [V, C.c_int64, V, V]),
         'trav_steps': (C.c_int, [V, I, I, I, V, I, V, V]),
         'fit_first_hit': (C.c_int, [V, V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I, I, I, I, V, V, V]),
     }

@@ -178,6 +178,17 @@ class HipBackend:
         B, P, N = theta_ba.shape
         self._metrics('vo_cones', theta_ba.data_ptr(), half.data_ptr(), collided.data_ptr(), B, N, P, cone.data_ptr())
 
+    def vo_cones_arg(self, theta_ba, arg, collided, half, cone):
+        """d2d_vo_cones_arg: theta_ba, arg [B, P, N], collided [B, P] -> half [B, P, N] (or None: not kept) and cone [B, P, N, 2];
+        the half angle asin(arg) is taken on the device"""
+        B, P, N = theta_ba.shape
+        self._metrics('vo_cones_arg', theta_ba.data_ptr(), arg.data_ptr(), collided.data_ptr(), B, N, P,
+                      None if half is None else half.data_ptr(), cone.data_ptr())
+
+    def asin_array(self, x, out):
+        """d2d_asin_array: out[i] = libm's asin(x[i]) on the device (NaN for |x| > 1); float64, out may be x"""
+        self._metrics('asin_array', x.data_ptr(), x.numel(), out.data_ptr())
+
     def vo_count(self, agents, cand, cone, collided, count):
         """d2d_vo_count: agents [B, 6, N], cand [C, 2], cone, collided -> count [B, P] int32 (-1: collided position)"""
         B, P, N, _ = cone.shape

@@ -4,7 +4,10 @@
 // The velocity-obstacle feasibility metric:
 //   geometry    thread = (world, position, agent): arg and theta_ba, coalesced; a second small kernel, thread = (world, position),
 //               ORs the collision test over the agents.
-//   cones       thread = (world, position, agent): two sin, two cos, two atan2.
+//   cones       thread = (world, position, agent): two sin, two cos, two atan2.  d2d_vo_cones reads the half angle, d2d_vo_cones_arg
+//               takes it first (d2d_asin.h: up to 15 table doubles of one row, or a seed and a division).  The asin tables stay in
+//               global memory (__device__ const, 21 KB): a lane gathers one row of at most 120 B, neighbouring agents' rows differ,
+//               and 256 threads would have to copy all 21 KB to LDS to read 256 rows of it; the whole table stays in L2.
 //   count       one wave per (world, 64 candidates, 64 positions); lane = candidate.  theta_dif of the wave's candidates against a
 //               tile of VO_TILE agents goes to LDS once ([tile][64] doubles), then the wave walks its positions: the cone pairs of
 //               (position, tile) arrive with one coalesced load (lane 2a = right, 2a + 1 = left of agent a) and reach every lane
@@ -36,6 +39,8 @@
 #define D2D_SINCOS_TBL_QUAL __device__ const
 #define D2D_ATAN2_QUAL __device__ __forceinline__
 #define D2D_ATAN2_TBL_QUAL __device__ const
+#define D2D_ASIN_QUAL __device__ __forceinline__
+#define D2D_ASIN_TBL_QUAL __device__ const
 #include "d2d_vo.h"
 #define D2D_DF_QUAL __device__ __forceinline__
 #include "d2d_difficulty.h"
@@ -114,6 +119,28 @@ __global__ __launch_bounds__(EW_BLOCK) void vo_cones_kernel(const double *__rest
   if (!collided[i / N]) d2d_vo_cone(theta_ba[i], half[i], &r, &l);
   cone[2 * i] = r;
   cone[2 * i + 1] = l;
+}
+
+template <bool HALF_OUT>
+__global__ __launch_bounds__(EW_BLOCK) void vo_cones_arg_kernel(const double *__restrict__ theta_ba, const double *__restrict__ arg,
+                                                               const uint8_t *__restrict__ collided, int N, long long total,
+                                                               double *__restrict__ half_out, double *__restrict__ cone) {
+  const long long i = (long long)blockIdx.x * EW_BLOCK + threadIdx.x;
+  if (i >= total) return;
+  const bool hit = collided[i / N];
+  double r = 0.0, l = 0.0;
+  if (HALF_OUT || !hit) {                       // (a collided position's half angles are only ever read through half_out)
+    const double half = d2d_vo_half(arg[i]);
+    if (HALF_OUT) half_out[i] = half;
+    if (!hit) d2d_vo_cone(theta_ba[i], half, &r, &l);
+  }
+  cone[2 * i] = r;
+  cone[2 * i + 1] = l;
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void asin_array_kernel(const double *x, long long n, double *out) {   // out may alias x
+  const long long i = (long long)blockIdx.x * EW_BLOCK + threadIdx.x;
+  if (i < n) out[i] = d2d_asin(x[i]);
 }
 
 __global__ __launch_bounds__(EW_BLOCK) void vo_count_init_kernel(const uint8_t *__restrict__ collided, long long BP, int32_t *__restrict__ count) {
@@ -277,6 +304,28 @@ int d2d_vo_cones(const double *theta_ba, const double *half, const uint8_t *coll
   hipLaunchKernelGGL(vo_cones_kernel, dim3(blocks_of(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, theta_ba, half, collided, (int)N,
                      total, cone);
   return launched("d2d_vo_cones");
+}
+
+int d2d_vo_cones_arg(const double *theta_ba, const double *arg, const uint8_t *collided, int32_t B, int32_t N, int32_t P,
+                     double *half_out, double *cone, void *stream) {
+  if (const int rc = check_sizes("d2d_vo_cones_arg", B, N, P, 1)) return rc;
+  if (!theta_ba || !arg || !collided || !cone) return fail(-1, "d2d_vo_cones_arg: a pointer is NULL");
+  const long long total = (long long)B * P * N;
+  if (half_out)
+    hipLaunchKernelGGL(vo_cones_arg_kernel<true>, dim3(blocks_of(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, theta_ba, arg, collided,
+                       (int)N, total, half_out, cone);
+  else
+    hipLaunchKernelGGL(vo_cones_arg_kernel<false>, dim3(blocks_of(total)), dim3(EW_BLOCK), 0, (hipStream_t)stream, theta_ba, arg, collided,
+                       (int)N, total, half_out, cone);
+  return launched("d2d_vo_cones_arg");
+}
+
+int d2d_asin_array(const double *x, int64_t n, double *out, void *stream) {
+  if (n < 0 || !x || !out) return fail(-1, "d2d_asin_array: n >= 0 and no NULL pointer");
+  if (n > (int64_t)D2D_VO_MAX_ELEMS * EW_BLOCK) return fail(-4, "d2d_asin_array: n <= (2^31 - 1) * 256");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(asin_array_kernel, dim3(blocks_of(n)), dim3(EW_BLOCK), 0, (hipStream_t)stream, x, (long long)n, out);
+  return launched("d2d_asin_array");
 }
 
 int d2d_vo_count(const double *agents, const double *cand, const double *cone, const uint8_t *collided, int32_t B, int32_t N, int32_t P,

@@ -8,7 +8,8 @@
  *                                                      fma(y, y, x * x) with x = pA.x - pB.x, y = pA.y - pB.y
  *   theta_BA  = math.atan2(pB.y - pA.y, pB.x - pA.x)
  *   collided  = dist < rA + rB
- *   arg       = (rA + rB) / dist                      asin(arg) is the cone's half angle (taken by the host's libm)
+ *   arg       = (rA + rB) / dist
+ *   half      = math.asin(arg)                        the cone's half angle: d2d_asin.h on the device, or the host's libm
  *   left      = math.atan2(sin(theta_BA + half), cos(theta_BA + half))
  *   right     = math.atan2(sin(theta_BA - half), cos(theta_BA - half))
  *   theta_dif = math.atan2(v.y - vB.y, v.x - vB.x)    per (candidate velocity v, agent): no position in it
@@ -39,8 +40,12 @@
 #ifndef D2D_ATAN2_QUAL
 #define D2D_ATAN2_QUAL D2D_VO_QUAL
 #endif
+#ifndef D2D_ASIN_QUAL
+#define D2D_ASIN_QUAL D2D_VO_QUAL
+#endif
 #include "../d2d_atan2.h"
 #include "../d2d_sincos.h"
+#include "d2d_asin.h"
 
 /* numpy.linalg.norm of the 2-vector (x, y) */
 D2D_VO_QUAL double d2d_vo_norm(double x, double y) { return __builtin_sqrt(D2D_FMA(y, y, x * x)); }
@@ -58,6 +63,10 @@ D2D_VO_QUAL int d2d_vo_pair(double ax, double ay, double bx, double by, double r
 D2D_VO_QUAL int d2d_vo_hits(double ax, double ay, double bx, double by, double rA, double rB) {
   return d2d_vo_norm(ax - bx, ay - by) < rA + rB;
 }
+
+/* vo_calculator.py:87: the half angle of one pair.  arg > 1 only for a pair that touches, whose position is in collision: the
+ * reference never evaluates it (math.asin would raise), the host path (metrics.host_asin) writes 0 there and so does this. */
+D2D_VO_QUAL double d2d_vo_half(double arg) { return arg > 1.0 ? 0.0 : d2d_asin(arg); }
 
 /* vo_calculator.py:88-91 and :107-108: the cone's edges as the script's atan2 of (sin, cos) returns them */
 D2D_VO_QUAL void d2d_vo_cone(double theta_ba, double half, double *right, double *left) {
@@ -86,7 +95,7 @@ D2D_VO_QUAL int d2d_vo_in_between(double right, double dif, double left) {
 }
 
 #if !defined(__HIPCC__) && !defined(__HIP_DEVICE_COMPILE__)
-/* ---- the three entry points as plain loops over host arrays (tests/csrc/vo_host.c), same layouts as include/d2d_metrics.h ---- */
+/* ---- the entry points as plain loops over host arrays (tests/csrc/vo_host.c), same layouts as include/d2d_metrics.h ---- */
 
 D2D_VO_QUAL void d2d_vo_geometry_seq(const double *agents, const double *pos, double rA, int B, int N, int P, double *arg,
                                      double *theta_ba, uint8_t *collided) {
@@ -111,6 +120,19 @@ D2D_VO_QUAL void d2d_vo_cones_seq(const double *theta_ba, const double *half, co
       const size_t o = bp * N + j;
       cone[2 * o] = cone[2 * o + 1] = 0.0;
       if (!collided[bp]) d2d_vo_cone(theta_ba[o], half[o], cone + 2 * o, cone + 2 * o + 1);
+    }
+}
+
+/* d2d_vo_cones_arg: the half angle taken here; half_out may be NULL */
+D2D_VO_QUAL void d2d_vo_cones_arg_seq(const double *theta_ba, const double *arg, const uint8_t *collided, int B, int N, int P,
+                                      double *half_out, double *cone) {
+  for (size_t bp = 0; bp < (size_t)B * P; ++bp)
+    for (int j = 0; j < N; ++j) {
+      const size_t o = bp * N + j;
+      const double half = d2d_vo_half(arg[o]);
+      if (half_out) half_out[o] = half;
+      cone[2 * o] = cone[2 * o + 1] = 0.0;
+      if (!collided[bp]) d2d_vo_cone(theta_ba[o], half, cone + 2 * o, cone + 2 * o + 1);
     }
 }
 

@@ -3,8 +3,10 @@
 vo_calculator.py builds, for each seeded world and each of 16 x 16 drone positions, the velocity-obstacle cone of every agent and
 asks for 63 x 10 candidate velocities whether any cone contains them; the fraction of free candidates is the position's rate, the
 mean over the positions the world's metric (vo.csv).  Here the worlds of a batch, their positions and the candidates are three
-launches of include/d2d_metrics.h (geometry, cones, count) with one host step between the first two: the cone's half angle
-asin((rA + rB) / dist) goes through the host's libm over the flat array, because the device has no bit-exact asin yet.
+launches of include/d2d_metrics.h (geometry, cones, count) with nothing between them: the cone's half angle asin((rA + rB) / dist)
+is taken inside the second launch by the device's restatement of libm's asin (asin='device', the default; device_asin() is that
+function alone).  asin='host' is the earlier path, with the same bits: the half angle goes through the host's libm over the flat
+array between the first two launches (host_asin).
 
     rates = vo_feasibility_batch(indices)          # [len(indices), 256]: per-position rates, 0 where the position is in collision
     metric = vo_feasibility(index)                 # np.mean(rates), as env_metrics(index) returns it
@@ -101,11 +103,37 @@ def host_asin(arg):
     return np.array([0.0 if v > 1.0 else asin(v) for v in flat], dtype=np.float64).reshape(arg.shape)
 
 
-def vo_counts(agents, positions, cand, rA=R_A, backend=None, return_parts=False, timings=None):
-    """The three launches plus the host asin.  agents [B, 6, N] (the state's layout), positions [P, 2], cand [C, 2]: float64 tensors
-    on the backend's device.  Returns count [B, P] int32 (the suitable candidates; -1: the position is inside an agent's disc); with
-    `return_parts` also a dict of arg, theta_ba, half [B, P, N], collided [B, P] and cone [B, P, N, 2].  `timings`: a dict that
-    receives geometry_s, asin_s (D2H, asin, H2D), cones_s, count_s, each synchronised on both sides."""
+ASIN_PATHS = ('device', 'host')
+
+
+def _asin_path(who, asin):
+    if asin not in ASIN_PATHS:
+        raise ValueError(f'{who}: asin={asin!r}: \'device\' (the half angle inside the cones launch) or \'host\' (libm between the launches)')
+    return asin
+
+
+def device_asin(x, backend=None):
+    """libm's asin of a float64 tensor on the backend's device, bit for bit (d2d_asin_array): what math.asin returns for every
+    element of [-1, 1], NaN for NaN and where math.asin raises (|x| > 1).  Returns a new tensor of x's shape."""
+    backend = _backend_of(backend, x.device, VO_SCRIPT)
+    if x.dtype != torch.float64:
+        raise ValueError('device_asin: a float64 tensor')
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    if x.numel():                          # (an empty tensor has no storage: its pointer is NULL, which the library refuses)
+        backend.asin_array(x, out)
+    return out
+
+
+def vo_counts(agents, positions, cand, rA=R_A, backend=None, return_parts=False, timings=None, asin='device'):
+    """The three launches.  agents [B, 6, N] (the state's layout), positions [P, 2], cand [C, 2]: float64 tensors on the backend's
+    device.  Returns count [B, P] int32 (the suitable candidates; -1: the position is inside an agent's disc); with `return_parts`
+    also a dict of arg, theta_ba, half [B, P, N], collided [B, P] and cone [B, P, N, 2].  `asin`: 'device' takes the half angle
+    inside the cones launch (d2d_vo_cones_arg; nothing crosses to the host), 'host' between the launches through the host's libm
+    (host_asin, then d2d_vo_cones); the results are the same bits.  `timings`: a dict that receives geometry_s, asin_s (D2H, asin,
+    H2D; 0.0 with asin='device', where cones_s covers the asin and the cones in their one launch), cones_s, count_s, each
+    synchronised on both sides."""
+    _asin_path('vo_counts', asin)
     backend = _backend_of(backend, agents.device, VO_SCRIPT)
     dev = agents.device
     agents = agents.contiguous()
@@ -128,9 +156,14 @@ def vo_counts(agents, positions, cand, rA=R_A, backend=None, return_parts=False,
     t0 = mark()
     backend.vo_geometry(agents, positions, rA, arg, theta_ba, collided)
     t1 = mark()
-    half = torch.from_numpy(host_asin(arg.cpu().numpy())).to(dev)
-    t2 = mark()
-    backend.vo_cones(theta_ba, half, collided, cone)
+    if asin == 'device':
+        t2 = t1
+        half = torch.empty((B, P, N), dtype=torch.float64, device=dev) if return_parts else None
+        backend.vo_cones_arg(theta_ba, arg, collided, half, cone)
+    else:
+        half = torch.from_numpy(host_asin(arg.cpu().numpy())).to(dev)
+        t2 = mark()
+        backend.vo_cones(theta_ba, half, collided, cone)
     t3 = mark()
     backend.vo_count(agents, cand, cone, collided, count)
     t4 = mark()
@@ -141,13 +174,14 @@ def vo_counts(agents, positions, cand, rA=R_A, backend=None, return_parts=False,
     return count
 
 
-def vo_feasibility_batch(indices, position_step=30, device='cuda:0', backend=None, worlds=None, timings=None):
+def vo_feasibility_batch(indices, position_step=30, device='cuda:0', backend=None, worlds=None, timings=None, asin='device'):
     """Per-position rates of several settings that share agent_number (same N), one chain of launches: float64
     [len(indices), P], count / C, 0 where the position is in collision (vo_calculator.py:95-97, :116), positions x-outermost.
     `worlds`: None (built here on the host, with drone_radius=0), a list of host worlds of `indices` built with _params(index), or
-    'device' (built by the device, vec_env.build_worlds_device_of).
+    'device' (built by the device, vec_env.build_worlds_device_of).  `asin`: as in vo_counts.
     `timings`: a dict that collects, per call, build_s, geometry_s, asin_s, cones_s, count_s and post_s (each synchronised on both
-    sides) under 'batches', and their totals."""
+    sides) under 'batches', and their totals; asin_s is 0.0 with asin='device' (cones_s covers the fused launch)."""
+    _asin_path('vo_feasibility_batch', asin)
     backend = _backend_of(backend, device, VO_SCRIPT)
     t_build = time.perf_counter()
     plist = [_params(ix) for ix in indices]
@@ -160,7 +194,7 @@ def vo_feasibility_batch(indices, position_step=30, device='cuda:0', backend=Non
         backend.sync()
     rec = {} if timings is not None else None
     t_dev = time.perf_counter()
-    count = vo_counts(agents, torch.from_numpy(pos).to(dev), torch.from_numpy(cand).to(dev), R_A, backend, timings=rec)
+    count = vo_counts(agents, torch.from_numpy(pos).to(dev), torch.from_numpy(cand).to(dev), R_A, backend, timings=rec, asin=asin)
     t_post = time.perf_counter()
     cnt = count.cpu().numpy()
     C = len(cand)
@@ -172,9 +206,9 @@ def vo_feasibility_batch(indices, position_step=30, device='cuda:0', backend=Non
     return rates
 
 
-def vo_feasibility(index, position_step=30, device='cuda:0', backend=None, worlds=None):
+def vo_feasibility(index, position_step=30, device='cuda:0', backend=None, worlds=None, asin='device'):
     """Drop-in for env_metrics(index) of vo_calculator.py:36-120: np.mean of the per-position rates."""
-    return np.mean(vo_feasibility_batch([index], position_step, device, backend, worlds)[0])
+    return np.mean(vo_feasibility_batch([index], position_step, device, backend, worlds, asin=asin)[0])
 
 
 def _table(who, order, map_ids, agent_numbers, worlds, batch):
@@ -186,14 +220,18 @@ def _table(who, order, map_ids, agent_numbers, worlds, batch):
 
 
 def vo_table(map_ids=range(20), agent_numbers=(10, 20, 30), agent_sizes=(5, 10, 15), agent_speeds=(20, 40, 60), position_step=30,
-             device='cuda:0', backend=None, worlds=None, timings=None):
+             device='cuda:0', backend=None, worlds=None, timings=None, asin='device'):
     """The nested list the reference writes to vo.csv (vo_calculator.py:122-136), in its loop order: one row per map_id, each with
-    product(agent_num, agent_size, agent_vel) metrics.  `worlds`: None, 'device', or one host world per setting in that order."""
+    product(agent_num, agent_size, agent_vel) metrics.  `worlds`: None, 'device', or one host world per setting in that order.
+    `asin`: as in vo_counts."""
+    _asin_path('vo_table', asin)
     map_ids = list(map_ids)
     order = _table_order(map_ids, agent_numbers, agent_sizes, agent_speeds)
 
+    kw = {} if asin == 'device' else dict(asin=asin)      # the default path through the batch function's earlier signature
+
     def batch(indices, w):
-        return [np.mean(r) for r in vo_feasibility_batch(indices, position_step, device, backend, w, timings)]
+        return [np.mean(r) for r in vo_feasibility_batch(indices, position_step, device, backend, w, timings, **kw)]
     return _table('vo_table', order, map_ids, agent_numbers, worlds, batch)
 
 

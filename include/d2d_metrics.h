@@ -7,13 +7,15 @@
  * velocities, the number of candidates that lie in no agent's velocity-obstacle cone.
  *
  *   d2d_vo_geometry   :74-85   dist, theta_BA, the collision test        -> arg = (rA + rB) / dist, theta_ba, collided
- *   (host)            :87      half = asin(arg) through the host's libm, over the flat array
- *   d2d_vo_cones      :88-91, :107-108   the cone's edges                -> cone = (theta_right, theta_left)
+ *   d2d_vo_cones_arg  :87-91, :107-108   half = asin(arg), the cone's edges -> cone = (theta_right, theta_left), half
+ *   (d2d_vo_cones     :88-91, :107-108   the cone's edges from a `half` the caller supplies: the earlier form of that step)
  *   d2d_vo_count      :101-116 the candidates no cone contains           -> count
  *
- * `half` is an INPUT of d2d_vo_cones because the device has no bit-exact restatement of libm's asin yet (csrc/ restates sin,
- * cos, atan2, tan, log and pow(x, 2.0)); everything else of the metric runs on the device.  A later change that adds one can drop
- * the round trip without touching d2d_vo_geometry, d2d_vo_cones' arithmetic or d2d_vo_count.
+ * asin is csrc/metrics/d2d_asin.h, a restatement of the host libm's asin that returns its bits (as csrc/ restates sin, cos, atan2,
+ * tan, log and pow(x, 2.0)): the whole metric runs on the device, nothing crosses to the host between the launches.
+ * d2d_vo_cones is the earlier form of the middle step, with `half` as an INPUT that the caller takes through the host's libm
+ * (metrics.host_asin) between d2d_vo_geometry and it; both forms give the same bits.  d2d_asin_array is the test hook of the asin
+ * alone.
  *
  * theta_dif = atan2(v.y - vB.y, v.x - vB.x) of vo_calculator.py:106 depends on the candidate and the agent only: d2d_vo_count
  * evaluates it once per (world, candidate, agent) and chunk of positions, not per position.  The script's `break` at :111 only
@@ -73,6 +75,17 @@ int d2d_vo_geometry(const double *agents, const double *pos, double rA, int32_t 
  * (0, 0) for every agent of a collided position. */
 int d2d_vo_cones(const double *theta_ba, const double *half, const uint8_t *collided, int32_t B, int32_t N, int32_t P, double *cone,
                  void *stream);
+
+/* d2d_vo_cones with the half angle taken on the device: half = arg > 1 ? 0 : asin(arg) (csrc/metrics/d2d_asin.h), arg as
+ * d2d_vo_geometry wrote it.  half_out: [B][P][N] or NULL; it receives the half angle of EVERY pair, those of collided positions
+ * included (what metrics.host_asin produces), cone as d2d_vo_cones.  Every entry of cone, and of half_out when given, is written
+ * whatever the buffers held.  Sizes and errors as d2d_vo_cones. */
+int d2d_vo_cones_arg(const double *theta_ba, const double *arg, const uint8_t *collided, int32_t B, int32_t N, int32_t P,
+                     double *half_out, double *cone, void *stream);
+
+/* test hook: out[i] = d2d_asin(x[i]), libm's asin (NaN for NaN and for |x| > 1, where Python's math.asin raises); n >= 0
+ * (0: no launch), n <= (2^31 - 1) * 256 (-4 otherwise); out may alias x. */
+int d2d_asin_array(const double *x, int64_t n, double *out, void *stream);
 
 /* agents [B][6][N] (rows VX, VY), cand [C][2] (vx, vy), cone, collided -> count [B][P] (i32): the candidates for which no agent's
  * in_between(theta_right, theta_dif, theta_left) holds, or -1 for a collided position.  Every entry is written by the call
