@@ -167,3 +167,19 @@ def bind_metrics(lib):
         'fit_first_hit': (C.c_int, [V, V, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I, I, I, I, V, V, V]),
     }
     return dict(_bind(lib, 'd2d_metrics_', own), **_bind(lib, 'd2d_', sig))
+
+
+# ---- include/d2d_rvo.h: the RVO motion profile on the device (csrc/rvo/libd2d_rvo.so, its own version) ----
+D2D_RVO_VERSION = 1
+RVO_MAX_CONES, RVO_MAX_ELEMS = 1024, 0x7fffffff
+
+
+def bind_rvo(lib):
+    """argtypes / restypes of include/d2d_rvo.h on a loaded CDLL."""
+    V, I, D = C.c_void_p, C.c_int32, C.c_double
+    own = {'version': (C.c_int, []), 'last_error': (C.c_char_p, [])}
+    sig = {
+        'velocity': (C.c_int, [V, V, V, I, I, I, V, V]),
+        'agents_step': (C.c_int, [V, V, D, D, D, D, I, I, V]),
+    }
+    return _bind(lib, 'd2d_rvo_', dict(own, **sig))

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('D2D_LIB') or os.path.join(_HERE, 'csrc', 'libd2d_hip.so')   # D2D_LIB: A/B builds
 WORLDS_LIB_PATH = os.path.join(_HERE, 'csrc', 'worlds', 'libd2d_worlds.so')             # include/d2d_worlds.h
 METRICS_LIB_PATH = os.path.join(_HERE, 'csrc', 'metrics', 'libd2d_metrics.so')          # include/d2d_metrics.h
+RVO_LIB_PATH = os.path.join(_HERE, 'csrc', 'rvo', 'libd2d_rvo.so')                      # include/d2d_rvo.h
 
 
 class D2DError(RuntimeError):
@@ -31,6 +32,7 @@ _LIBRARIES = {
     'libd2d_hip.so': (A.bind, 'abi_version', 'D2D_ABI_VERSION', 'ABI', 'build.sh'),
     'libd2d_worlds.so': (A.bind_worlds, 'version', 'D2D_WORLDS_VERSION', 'version', 'worlds/build.sh'),
     'libd2d_metrics.so': (A.bind_metrics, 'version', 'D2D_METRICS_VERSION', 'version', 'metrics/build.sh'),
+    'libd2d_rvo.so': (A.bind_rvo, 'version', 'D2D_RVO_VERSION', 'version', 'rvo/build.sh'),
 }
 
 
@@ -64,6 +66,11 @@ def load_metrics_library(path=METRICS_LIB_PATH):
     return _load('libd2d_metrics.so', path)
 
 
+def load_rvo_library(path=RVO_LIB_PATH):
+    """The RVO motion profile's own library (include/d2d_rvo.h)."""
+    return _load('libd2d_rvo.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -89,6 +96,7 @@ class HipBackend:
     supports_device_worlds = True         # include/d2d_worlds.h: the seeded worlds are built on the device
     supports_vo_metric = True             # include/d2d_metrics.h: the velocity-obstacle feasibility metric (metrics.py)
     supports_difficulty_tables = True     # include/d2d_metrics.h: the traversability and survival-fit metrics (metrics.py)
+    supports_rvo = True                   # include/d2d_rvo.h: the RVO motion profile (VecDrone2DEnv with motion_profile='RVO')
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -99,6 +107,7 @@ class HipBackend:
         self.lib, self.fn = load_library()
         self.wlib, self.wfn = load_worlds_library()
         self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
+        self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -206,6 +215,22 @@ class HipBackend:
         B, _, N = agents.shape
         self._metrics('fit_first_hit', agents.data_ptr(), pos.data_ptr(), float(drone_radius), float(W_px), float(H_px), float(scale),
                       float(dt), B, N, pos.shape[0], int(checks), first.data_ptr(), None if agents_out is None else agents_out.data_ptr())
+
+    def _rvo(self, name, *args):
+        if self.rfn is None:
+            self.rlib, self.rfn = load_rvo_library()
+        _check(self.rfn[name](*args, self._stream()), self.rfn, 'd2d_rvo')
+
+    def rvo_velocity(self, agents, vel, pillars, vel_out):
+        """d2d_rvo_velocity: agents [B, 6, N], vel [B, 2, N] float64, pillars [B, P, 3] int32 -> vel_out [B, 2, N] (not vel)"""
+        B, _, N = agents.shape
+        P = pillars.shape[1]
+        self._rvo('velocity', agents.data_ptr(), vel.data_ptr(), pillars.data_ptr() if P else None, B, N, P, vel_out.data_ptr())
+
+    def rvo_agents_step(self, agents, vel, W_px, H_px, scale, dt):
+        """d2d_rvo_agents_step: Agent.step of agents [B, 6, N] in place, moving with vel [B, 2, N]"""
+        B, _, N = agents.shape
+        self._rvo('agents_step', agents.data_ptr(), vel.data_ptr(), float(W_px), float(H_px), float(scale), float(dt), B, N)
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -3,7 +3,7 @@
  *
  * Reference call sites: vo_calculator.py:87 `half_angle = math.asin((rA + rB) / dist)` (the velocity-obstacle cone's half angle;
  * the cone's edges are then compared with other angles, so the device has to return libm's bits, not just an accurate angle) and
- * utils.py:327, :346, :423 (the RVO motion profile, which does not run on the device).
+ * utils.py:327, :346, :423 (the RVO motion profile: csrc/rvo/d2d_rvo.h includes this file unchanged).
  *
  * math.asin (CPython Modules/mathmodule.c, math_1 over libm's asin) returns NaN for NaN and RAISES ValueError for |x| > 1, where
  * libm returns NaN; d2d_asin returns libm's NaN there.  The velocity-obstacle caller never passes such a value (d2d_vo_half).

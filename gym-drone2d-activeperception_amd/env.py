@@ -127,7 +127,8 @@ class _ArchivedTracker:
 
 
 class AgentProxy:
-    """Agent view (utils.py:461-493).  Under CVM velocity IS pref_velocity (drone_v2.py:178)."""
+    """Agent view (utils.py:461-493).  Under CVM velocity IS pref_velocity (drone_v2.py:178); under RVO it is the velocity
+    RVO_update assigned in the last step (utils.py:356)."""
 
     def __init__(self, env, k):
         self._env, self._k = env, k
@@ -146,7 +147,22 @@ class AgentProxy:
 
     position = property(lambda s: s._get(A.A_PX, A.A_PY), lambda s, v: s._set(A.A_PX, A.A_PY, v))
     pref_velocity = property(lambda s: s._get(A.A_VX, A.A_VY), lambda s, v: s._set(A.A_VX, A.A_VY, v))
-    velocity = pref_velocity
+
+    @property
+    def velocity(self):
+        if not self._env._vec.rvo:
+            return self.pref_velocity
+        v = self._env._mirror['agent_vel']
+        return np.array([v[0, self._k], v[1, self._k]])
+
+    @velocity.setter
+    def velocity(self, v):
+        if not self._env._vec.rvo:
+            self.pref_velocity = v
+            return
+        vel = self._env._mirror['agent_vel']
+        vel[:, self._k] = np.asarray(v, dtype=np.float64).ravel()[:2]
+        self._env._push('agent_vel', vel)
 
     @property
     def radius(self):
@@ -233,8 +249,6 @@ class Drone2DEnv2(_EnvBase):
     def _build(self, params):
         self.params = with_defaults(params)
         p = self.params
-        if p.motion_profile != 'CVM':
-            raise NotImplementedError('motion_profile RVO is outside the accelerated hot path (SURVEY.md section 2)')
         planner_cls = planner_list[p.planner]                       # KeyError for an unknown name, as the reference
         on_device = bool(getattr(planner_cls, 'on_device', False))
         self._mode = ('fused' if p.planner == 'NoMove' else 'device') if on_device else 'host'
@@ -284,7 +298,7 @@ class Drone2DEnv2(_EnvBase):
     def _pull(self, only=None):
         """ONE device-to-host copy: the mirrored fields of this env packed into a byte buffer on the device."""
         vec, slot = self._vec, self._slot
-        parts = [(k, vec.state.t[k][slot]) for k in (only or self._MIRROR_STATE)]
+        parts = [(k, vec.state.t[k][slot]) for k in (only or (('agent_vel',) if vec.rvo else ()) + self._MIRROR_STATE)]
         if vec.plugins is not None and only is None:
             parts += [(k, vec.plugins.t[k][slot]) for k in self._MIRROR_PLUGIN]
         flat = torch.cat([t.reshape(-1).view(torch.uint8) for _, t in parts]).cpu().numpy()
@@ -355,9 +369,9 @@ class Drone2DEnv2(_EnvBase):
         np.random.randn(2) for the agents the rays hit, in agent order (utils.py:603-605)."""
         vec = self._vec
         if self.params.var_cam == 0 or vec.N == 0:
-            vec.backend.perceive(vec.cfg, vec._st)
+            vec.run_perceive()
             return
-        vec.backend.run_stages(vec.cfg, vec._st, A.ST_FSM | A.ST_AGENTS | A.ST_RAYCAST)
+        vec.run_perceive(A.ST_FSM | A.ST_AGENTS | A.ST_RAYCAST)
         self._pull(only=('hit',))
         noise = np.zeros((1, vec.N, 2))
         for k in np.nonzero(self._mirror['hit'])[0]:
@@ -380,7 +394,7 @@ class Drone2DEnv2(_EnvBase):
         elif self.params.var_cam != 0 and vec.N:
             self._perceive()
         else:
-            vec.backend.step(vec.cfg, vec._st)                         # fused: perceive + act in one launch
+            vec.run_step()                                             # fused: perceive + act in one launch (RVO: the agents first)
             self._pull()
             return self._finish_step()
         vec.backend.act(vec.cfg, vec._st)

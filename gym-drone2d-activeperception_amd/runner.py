@@ -84,6 +84,9 @@ class ExperimentBatch:
             raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / LookAhead / LookGoal / Owl / '
                                       'Rotating / NoControl, planner Primitive / NoMove (use Experiment, one episode at a time, for '
                                       'other host plugin classes)')
+        if p.motion_profile == 'RVO':
+            raise NotImplementedError("ExperimentBatch: motion_profile 'RVO' does not run inside the persistent closed loop (its stage "
+                                      'lives in libd2d_rvo.so); run the episodes through Experiment, one at a time')
         device_heading = device_gaze and getattr(backend if backend is not None else HipBackend, 'supports_device_heading_gaze', False)
         if p.gaze_method == 'LookGoal' and not device_heading:
             raise NotImplementedError('ExperimentBatch: LookGoal needs a backend with the device LookAhead / LookGoal stage')

@@ -65,6 +65,7 @@ def _spec(B, N, W, H, L, T, grid_tile=0):
 
 WORLD_FIELDS = ('agents', 'agent_unit', 'dyn_prev', 'gt', 'dmap', 'drone', 'target', 'targets', 'counters',
                 'active', 'kf', 'kf_len', 'rng')
+RVO_WORLD_FIELDS = ('agent_vel',)     # under motion_profile='RVO' (BatchState.init_rvo): part of the snapshot a reset restores
 RNG_FIELDS = ('rng', 'rng_draws')      # allocated only when var_cam != 0 (d2d_state.rng: the stream of the measurement noise)
 
 
@@ -184,11 +185,25 @@ class BatchState:
         if 'rng_draws' in self.t:
             self.t['rng_draws'].zero_()
 
+    def init_rvo(self, n_seeded, pillars, n_pillars):
+        """The fields of the RVO motion profile (include/d2d_rvo.h), none of them part of d2d_state: `agent_vel` [B, 2, N], the
+        agents' `velocity` -- zero for the `n_seeded` seeded agents, the preferred velocity for the static map's cell agents
+        (drone_v2.py:29-31, :61-66), a copy on the device from the agent planes the worlds were loaded into; `agent_vel_out`, the
+        buffer a step's decisions are written to before the two are swapped; `pillars` [B, P, 3] int32 from the worlds' obstacles
+        (P = `n_pillars`, given because a batch of no envs has no array to read it from)."""
+        B, N = self.cfg.B, self.cfg.N
+        vel = torch.zeros((B, 2, N), dtype=torch.float64, device=self.device)
+        vel[:, :, n_seeded:] = self.t['agents'][:, A.A_VX:A.A_VY + 1, n_seeded:]
+        self.t['agent_vel'] = vel
+        self.t['agent_vel_out'] = torch.zeros_like(vel)
+        pil = torch.as_tensor(np.asarray(pillars), dtype=torch.int32).reshape(B, int(n_pillars), 3)
+        self.t['pillars'] = pil.to(self.device).contiguous()
+
     def clone_world(self):
         """Snapshot of the world fields (reset source)."""
         snap = BatchState.__new__(BatchState)
         snap.cfg, snap.device, snap.noise, snap._dummy = self.cfg, self.device, None, self._dummy
-        snap.t = {k: (v.clone() if k in WORLD_FIELDS else v) for k, v in self.t.items()}
+        snap.t = {k: (v.clone() if k in WORLD_FIELDS + RVO_WORLD_FIELDS else v) for k, v in self.t.items()}
         return snap
 
     def struct(self, use_planner_inputs=True):

@@ -14,6 +14,13 @@ Planner modes
               (`closed_loop()`: gaze -> perceive -> plan -> act, no host round trip); `gaze='LookAhead'` / `'LookGoal'`
               (yaw_planner.py:18-39 / :225-257) and `gaze='Owl'` (:151-222) run on the device the same way on a backend
               that has them
+
+Motion profiles (`params.motion_profile`)
+  'CVM'       the agents move with their preferred velocity, inside the fused step (D2D_ST_AGENTS)
+  'RVO'       utils.py:299-460: every agent first picks a velocity outside the others' reciprocal velocity obstacles
+              (include/d2d_rvo.h, two launches of libd2d_rvo.so), then the fused step runs without its agents stage.
+              `step`, `perceive` / `act`, `rollout` and `reset` run it; `closed_loop` does not (the persistent kernel cannot take
+              a stage from another library)
 """
 import numpy as np
 import torch
@@ -216,7 +223,17 @@ class VecDrone2DEnv:
         self.env_offset = int(env_offset)
         planner = planner if planner is not None else self.params.planner
         self.planner_mode = A.PLANNER_NOMOVE if planner == 'NoMove' else A.PLANNER_EXTERNAL
+        profile = self.params.motion_profile
+        if profile not in ('CVM', 'RVO'):
+            raise ValueError(f"motion_profile {profile!r}: 'CVM' or 'RVO'")
+        self.rvo = profile == 'RVO'
+        if self.rvo and (self.params.agent_max_speed == 0 or self.params.agent_radius == -1):
+            # np.arange(0.02, 0 + 0.02, 0 / 5.0) raises in the reference's intersect(), outside RVO_update's try (utils.py:367)
+            raise NotImplementedError("motion_profile 'RVO' with agent_max_speed == 0 or agent_radius == -1: the reference itself "
+                                      'cannot run RVO with these parameters')
         self.backend = backend = backend_for(backend, device)
+        if self.rvo:
+            backend_for(backend, device, 'supports_rvo', "has no RVO motion profile (motion_profile='RVO' runs on the HIP backend)")
         self.device = torch.device(backend.device)
         # worlds='device' / a DeviceWorlds: the seeded worlds are built by the device (include/d2d_worlds.h) and never exist on the host;
         # N and T follow from the parameters and the static map
@@ -243,16 +260,24 @@ class VecDrone2DEnv:
         if dw is not None:
             self.state.load_device_worlds(dw)
             self.tracker_radius = dw.tracker_radius if dw.index is None else dw.tracker_radius[dw.index.cpu()]
+            pillars = dw.obstacles if dw.index is None else dw.obstacles[dw.index.cpu().numpy()]
         elif on_device:
-            self.tracker_radius = _build_into(backend, inp, self.state)[0] if self.num_envs else None
+            self.tracker_radius, pillars = _build_into(backend, inp, self.state)[:2] if self.num_envs else (None, np.zeros((0, 0, 3)))
         else:
             self.state.load_worlds(worlds)
+            pillars = None
+            if self.rvo:                       # (worlds built by hand for the constant-velocity model need not name their pillars)
+                if len({len(w['obstacles']) for w in worlds}) > 1:
+                    raise ValueError("motion_profile 'RVO': all envs of a batch must have the same number of pillars")
+                pillars = np.stack([w['obstacles'] for w in worlds]) if worlds else np.zeros((0, 0, 3))
             if worlds:
                 from .state import distinct_worlds
                 distinct, index = distinct_worlds(worlds)
                 self.tracker_radius = torch.from_numpy(np.stack([w['tracker_radius'] for w in distinct]))[torch.as_tensor(index)]
             else:
                 self.tracker_radius = None
+        if self.rvo:
+            self.state.init_rvo(min(int(self.params.agent_number), N), pillars, np.asarray(pillars).shape[1] if self.num_envs else self.params.pillar_number)
         self.init_state = self.state.clone_world()
         self._st = self.state.struct()
         self._init_st = self.init_state.struct()
@@ -304,8 +329,40 @@ class VecDrone2DEnv:
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
         self.backend.reset(self.cfg, self._st, self._init_st, mask)
+        if self.rvo:
+            vel, vel0 = self.state.agent_vel, self.init_state.agent_vel
+            vel.copy_(vel0 if mask is None else torch.where(mask.bool()[:, None, None], vel0, vel))
         self.reset_plugins(mask)
         return {}
+
+    def _rvo_agents(self):
+        """RVO_update + Agent.step of every env (include/d2d_rvo.h): the decisions read the positions and velocities of before the
+        step, so they are a launch of their own; the velocity buffers swap afterwards."""
+        s = self.state
+        if self.num_envs == 0:
+            return
+        self.backend.rvo_velocity(s.agents, s.agent_vel, s.pillars, s.agent_vel_out)
+        self.backend.rvo_agents_step(s.agents, s.agent_vel_out, self.cfg.W_px, self.cfg.H_px, self.cfg.scale, self.cfg.dt)
+        s.t['agent_vel'], s.t['agent_vel_out'] = s.t['agent_vel_out'], s.t['agent_vel']
+
+    def run_step(self):
+        """d2d_step with the action already set; under RVO the agents move first, then every other stage (the state machine stage,
+        which d2d_step runs before the agents, does not touch them: the order is the reference's)"""
+        if self.rvo:
+            self._rvo_agents()
+            self.backend.run_stages(self.cfg, self._st, A.ST_ALL & ~A.ST_AGENTS)
+        else:
+            self.backend.step(self.cfg, self._st)
+
+    def run_perceive(self, stages=A.ST_PERCEIVE):
+        """d2d_perceive, or the stages of it named; the agents stage is the RVO launches under RVO"""
+        if self.rvo and stages & A.ST_AGENTS:
+            self._rvo_agents()
+            stages &= ~A.ST_AGENTS
+        if stages == A.ST_PERCEIVE:
+            self.backend.perceive(self.cfg, self._st)
+        elif stages:
+            self.backend.run_stages(self.cfg, self._st, stages)
 
     def _set_action(self, actions):
         a = torch.as_tensor(actions, dtype=torch.float64)
@@ -339,12 +396,12 @@ class VecDrone2DEnv:
     def step(self, actions):
         """One fused Drone2DEnv2.step for every env.  Returns (obs, reward, done, info) of tensors."""
         self._set_action(actions)
-        self.backend.step(self.cfg, self._st)
+        self.run_step()
         return self._result()
 
     def perceive(self):
         """First half of step() (lines 153-187); a host planner plugin runs after this."""
-        self.backend.perceive(self.cfg, self._st)
+        self.run_perceive()
 
     def act(self, actions):
         """Second half of step() (lines 198-255)."""
@@ -364,6 +421,27 @@ class VecDrone2DEnv:
         if pin is not None:
             pin = torch.as_tensor(pin, dtype=torch.float64, device=self.device).contiguous()
         coll = torch.empty((T, self.num_envs), dtype=torch.uint8, device=self.device) if collisions else None
+        if self.rvo:
+            # a host loop of the RVO step (`streams` is ignored): pin = a copy into the drone record before each step, collisions =
+            # a copy of the flag after it, as d2d_rollout does them
+            # With a [rows, B, N, 2] block of draws step t of the run takes row (row0 + t) % rows, as d2d_rollout does.  A single
+            # d2d_run_stages reads the block's first row whatever noise_row0 says, so each step is handed its own row.
+            noise = self.state.noise if self.cfg.noise_rows > 1 else None
+            try:
+                for t in range(T):
+                    if pin is not None:
+                        self.state.drone[:, A.D_X:A.D_Y + 1] = pin
+                    self.state.action.copy_(actions[t])
+                    if noise is not None:
+                        self._st.noise = noise[self.cfg.noise_row0].data_ptr()
+                    self.run_step()
+                    self._advance_noise(1)
+                    if collisions:
+                        coll[t] = self.state.flags[:, A.F_COLLISION]
+            finally:
+                if noise is not None:
+                    self._st.noise = noise.data_ptr()
+            return coll
         S = max(1, min(int(streams), self.num_envs))
         if S == 1 or self.device.type != 'cuda' or (self.state.noise is not None and self.cfg.noise_rows > 1):
             self.backend.rollout(self.cfg, self._st, T, actions, pin, coll)
@@ -428,6 +506,10 @@ class VecDrone2DEnv:
         stays as it ended (one episode per env; `episode_stats()` then holds one CSV row per env)."""
         if self.plugins is None:
             raise RuntimeError('closed_loop() needs device_plugins=True')
+        if self.rvo:
+            raise NotImplementedError("closed_loop(): motion_profile 'RVO' does not run inside the persistent closed loop (its stage "
+                                      'lives in libd2d_rvo.so); step the env with step() / perceive() + act(), or run episodes '
+                                      'through runner.Experiment')
         mode = A.DONE_RESET if auto_reset else (A.DONE_FREEZE if freeze_done else A.DONE_CONTINUE)
         self.backend.closed_loop(self.cfg, self._st, self._plan, int(nsteps), mode,
                                  self._init_st if auto_reset else None)
