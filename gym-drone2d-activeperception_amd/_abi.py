@@ -183,3 +183,31 @@ def bind_rvo(lib):
         'agents_step': (C.c_int, [V, V, D, D, D, D, I, I, V]),
     }
     return _bind(lib, 'd2d_rvo_', dict(own, **sig))
+
+
+# ---- include/d2d_jerk.h: the Jerk_Primitive planner on the device (csrc/jerk/libd2d_jerk.so, its own version) ----
+D2D_JERK_VERSION = 1
+JERK_NTHETA, JERK_PATTERNS, JERK_MAX_S, JERK_MAX_N, JERK_TH_F, JERK_TT_F = 72, 288, 128, 1024, 8, 5
+JERK_STAT_TIE, JERK_STAT_UNKNOWN, JERK_STAT_SHIFT = 1, 2, 8
+JERK_CALL_POINTERS = ('drone', 'target', 'active', 'kf', 'dmap', 'trk_radius', 'trk_prev', 'th_tab', 'tt_tab', 'tie_perm', 'tie_eq',
+                      'plan_ok', 'wp_valid', 'wp', 'choice', 'stat')
+JERK_CALL_INT_FIELDS = ('B', 'N', 'S', 'W', 'H', 'grid_tile')
+JERK_CALL_F64_FIELDS = ('scale', 'W_px', 'H_px', 'drone_radius', 'agent_radius', 'var_cam', 'half_v_max')
+
+
+class JerkCall(C.Structure):
+    """include/d2d_jerk.h `d2d_jerk_call`."""
+    _fields_ = [(n, C.c_void_p) for n in JERK_CALL_POINTERS] + [(n, C.c_int32) for n in JERK_CALL_INT_FIELDS] + \
+               [(n, C.c_double) for n in JERK_CALL_F64_FIELDS]
+
+
+def bind_jerk(lib):
+    """argtypes / restypes of include/d2d_jerk.h on a loaded CDLL."""
+    V, I = C.c_void_p, C.c_int32
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'plan': (C.c_int, [C.POINTER(JerkCall), V]),
+        'reset': (C.c_int, [V, V, V, V, I, I, I, V]),
+    }
+    return _bind(lib, 'd2d_jerk_', sig)

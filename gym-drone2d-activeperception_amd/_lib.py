@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get('D2D_LIB') or os.path.join(_HERE, 'csrc', 'libd2d_hip.
 WORLDS_LIB_PATH = os.path.join(_HERE, 'csrc', 'worlds', 'libd2d_worlds.so')             # include/d2d_worlds.h
 METRICS_LIB_PATH = os.path.join(_HERE, 'csrc', 'metrics', 'libd2d_metrics.so')          # include/d2d_metrics.h
 RVO_LIB_PATH = os.path.join(_HERE, 'csrc', 'rvo', 'libd2d_rvo.so')                      # include/d2d_rvo.h
+JERK_LIB_PATH = os.path.join(_HERE, 'csrc', 'jerk', 'libd2d_jerk.so')                   # include/d2d_jerk.h
 
 
 class D2DError(RuntimeError):
@@ -33,6 +34,7 @@ _LIBRARIES = {
     'libd2d_worlds.so': (A.bind_worlds, 'version', 'D2D_WORLDS_VERSION', 'version', 'worlds/build.sh'),
     'libd2d_metrics.so': (A.bind_metrics, 'version', 'D2D_METRICS_VERSION', 'version', 'metrics/build.sh'),
     'libd2d_rvo.so': (A.bind_rvo, 'version', 'D2D_RVO_VERSION', 'version', 'rvo/build.sh'),
+    'libd2d_jerk.so': (A.bind_jerk, 'version', 'D2D_JERK_VERSION', 'version', 'jerk/build.sh'),
 }
 
 
@@ -71,6 +73,11 @@ def load_rvo_library(path=RVO_LIB_PATH):
     return _load('libd2d_rvo.so', path)
 
 
+def load_jerk_library(path=JERK_LIB_PATH):
+    """The Jerk_Primitive planner's own library (include/d2d_jerk.h)."""
+    return _load('libd2d_jerk.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -97,6 +104,7 @@ class HipBackend:
     supports_vo_metric = True             # include/d2d_metrics.h: the velocity-obstacle feasibility metric (metrics.py)
     supports_difficulty_tables = True     # include/d2d_metrics.h: the traversability and survival-fit metrics (metrics.py)
     supports_rvo = True                   # include/d2d_rvo.h: the RVO motion profile (VecDrone2DEnv with motion_profile='RVO')
+    supports_jerk = True                  # include/d2d_jerk.h: the Jerk_Primitive planner (VecDrone2DEnv with planner='Jerk_Primitive')
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -108,6 +116,7 @@ class HipBackend:
         self.wlib, self.wfn = load_worlds_library()
         self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
         self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
+        self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -231,6 +240,21 @@ class HipBackend:
         """d2d_rvo_agents_step: Agent.step of agents [B, 6, N] in place, moving with vel [B, 2, N]"""
         B, _, N = agents.shape
         self._rvo('agents_step', agents.data_ptr(), vel.data_ptr(), float(W_px), float(H_px), float(scale), float(dt), B, N)
+
+    def _jerk(self, name, *args):
+        if self.jfn is None:
+            self.jlib, self.jfn = load_jerk_library()
+        _check(self.jfn[name](*args, self._stream()), self.jfn, 'd2d_jerk')
+
+    def jerk_plan(self, call):
+        """d2d_jerk_plan: `call` is an _abi.JerkCall of device pointers (jerk_plugin.JerkState.call)"""
+        self._jerk('plan', C.byref(call))
+
+    def jerk_reset(self, trk_radius, trk_prev, trk_radius0, mask=None, mask_stride=1):
+        """d2d_jerk_reset: trk_radius [B, N] float64 <- trk_radius0, trk_prev [B, N] uint8 <- 0, for the envs of mask (or all)"""
+        B, N = trk_radius.shape
+        self._jerk('reset', trk_radius.data_ptr(), trk_prev.data_ptr(), trk_radius0.data_ptr(),
+                   None if mask is None else mask.data_ptr(), int(mask_stride), B, N)
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -229,9 +229,10 @@ class DroneProxy:
 
 
 class Drone2DEnv2(_EnvBase):
-    """Three step paths, chosen by the class `planner_list[params.planner]` resolves to:
+    """Four step paths, chosen by the class `planner_list[params.planner]` resolves to:
       device NoMove     one fused launch (d2d_step)
       device Primitive  d2d_perceive -> d2d_plan_stage -> d2d_act queued back to back, no host in between
+      device Jerk_Primitive  d2d_perceive -> d2d_jerk_plan -> d2d_act likewise (planners.enable_device_jerk())
       host plugin       d2d_perceive -> planner.replan_check / plan on the host -> d2d_act
     and ONE packed device-to-host copy per step refreshes the mirror the proxies read (two on the host-plugin path,
     whose planner needs this step's perception)."""
@@ -251,12 +252,16 @@ class Drone2DEnv2(_EnvBase):
         p = self.params
         planner_cls = planner_list[p.planner]                       # KeyError for an unknown name, as the reference
         on_device = bool(getattr(planner_cls, 'on_device', False))
-        self._mode = ('fused' if p.planner == 'NoMove' else 'device') if on_device else 'host'
+        jerk = on_device and getattr(planner_cls, '__name__', '') == 'Jerk_Primitive'
+        self._mode = ('fused' if p.planner == 'NoMove' else 'jerk' if jerk else 'device') if on_device else 'host'
+        if jerk and p.gaze_method == 'Oxford':
+            raise NotImplementedError("planner 'Jerk_Primitive' on the device with gaze_method 'Oxford': the device Oxford stage reads "
+                                      "the Primitive planner's state; register the reference's yaw_planner.Oxford as a host policy")
         want_gaze = on_device and p.gaze_method == 'Oxford'
-        plugins = self._mode == 'device' or want_gaze
+        plugins = self._mode in ('device', 'jerk') or want_gaze
         self._vec = VecDrone2DEnv(p, 1, device=self._device, backend=self._backend, grid_layout='rowmajor',   # the proxies index [W][H]
-                                  planner=p.planner if on_device else 'external', device_plugins=plugins,
-                                  gaze=('Oxford' if want_gaze else 'external') if plugins else None)
+                                  planner=('Jerk_Primitive' if jerk else p.planner) if on_device else 'external',
+                                  device_plugins=plugins, gaze=('Oxford' if want_gaze else 'external') if plugins else None)
         self._slot = 0
         self._device_gaze = want_gaze
         self._backend = self._vec.backend
@@ -301,6 +306,8 @@ class Drone2DEnv2(_EnvBase):
         parts = [(k, vec.state.t[k][slot]) for k in (only or (('agent_vel',) if vec.rvo else ()) + self._MIRROR_STATE)]
         if vec.plugins is not None and only is None:
             parts += [(k, vec.plugins.t[k][slot]) for k in self._MIRROR_PLUGIN]
+        if vec.jerk is not None and only is None:
+            parts += [('trk_radius', vec.jerk.t['trk_radius'][slot])]
         flat = torch.cat([t.reshape(-1).view(torch.uint8) for _, t in parts]).cpu().numpy()
         off = 0
         for k, t in parts:
@@ -391,6 +398,9 @@ class Drone2DEnv2(_EnvBase):
         elif self._mode == 'device':
             self._perceive()
             vec.backend.plan_stage(vec.cfg, vec._st, vec._plan)
+        elif self._mode == 'jerk':
+            self._perceive()
+            vec.run_jerk_plan()
         elif self.params.var_cam != 0 and vec.N:
             self._perceive()
         else:

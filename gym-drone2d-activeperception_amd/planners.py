@@ -7,7 +7,8 @@ What the reference's callers touch is kept:
 
 `Primitive` and `NoMove` ARE the device stages (csrc/d2d_plugins.h `plan_env`, D2D_PLANNER_NOMOVE): the objects
 registered here hold no algorithm, they are views of the env's device-resident planner state -- `env.step`
-runs `d2d_perceive -> d2d_plan_stage -> d2d_act` without coming back to the host in between.  Any other class
+runs `d2d_perceive -> d2d_plan_stage -> d2d_act` without coming back to the host in between.  `Jerk_Primitive` is a device
+planner too (`d2d_perceive -> d2d_jerk_plan -> d2d_act`, libd2d_jerk.so) once `enable_device_jerk()` has registered it.  Any other class
 with the reference's interface (the reference's own `traj_planner.Primitive`, a third-party planner) is a host
 plugin: register it with `register_planner` and `env.step` calls its replan_check / plan between the two
 device halves of the step.  Names this registry does not know are looked up in the reference's `traj_planner`
@@ -149,6 +150,19 @@ class Primitive(_DevicePlanner):
         self.trajectory = TrajectoryView(self._env)
 
 
+class Jerk_Primitive(_DevicePlanner):
+    """traj_planner.py:403-516 as the device launch `d2d_jerk_plan` (include/d2d_jerk.h, libd2d_jerk.so): the 72 headings are
+    ranked and their primitives tested between d2d_perceive and d2d_act.  The reference's planner appends one waypoint per plan()
+    and step_pos pops it in the same step, so the trajectory anybody can look at between two steps is empty.
+
+    Not in `planner_list` by default (the name then resolves to the reference's own class where that is importable, as before):
+    `enable_device_jerk()` registers it."""
+
+    def __init__(self, drone, params):
+        super().__init__(drone, params)
+        self.trajectory = HostTrajectory()
+
+
 class _Registry(dict):
     """Name -> class.  Unknown names fall back to the reference's own module when it is importable."""
     module, what = 'traj_planner', 'planner'
@@ -173,6 +187,15 @@ class _Registry(dict):
 
 
 planner_list = _Registry(Primitive=Primitive, NoMove=NoMove)
+
+
+def enable_device_jerk(on=True):
+    """Register (or, with on=False, remove) the device `Jerk_Primitive` under its name: `Params(planner='Jerk_Primitive')` then
+    runs d2d_perceive -> d2d_jerk_plan -> d2d_act inside Drone2DEnv2.step instead of the reference's Python class."""
+    if on:
+        planner_list['Jerk_Primitive'] = Jerk_Primitive
+    elif dict.get(planner_list, 'Jerk_Primitive') is Jerk_Primitive:
+        del planner_list['Jerk_Primitive']
 
 
 def register_planner(name, cls):

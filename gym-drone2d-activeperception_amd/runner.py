@@ -80,6 +80,10 @@ class ExperimentBatch:
         from .vec_env import VecDrone2DEnv, build_worlds
         from ._lib import HipBackend
         p = with_defaults(params)
+        if p.planner == 'Jerk_Primitive':
+            raise NotImplementedError("ExperimentBatch: planner 'Jerk_Primitive' does not run inside the persistent closed loop (its "
+                                      'stage lives in libd2d_jerk.so); step a VecDrone2DEnv(..., planner=\'Jerk_Primitive\', '
+                                      'device_plugins=True) with step(), or run the episodes through runner.Experiment, one at a time')
         if p.gaze_method not in ('Oxford', 'Rotating', 'NoControl', 'LookAhead', 'LookGoal', 'Owl') or p.planner not in ('Primitive', 'NoMove'):
             raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / LookAhead / LookGoal / Owl / '
                                       'Rotating / NoControl, planner Primitive / NoMove (use Experiment, one episode at a time, for '

@@ -14,6 +14,11 @@ Planner modes
               (`closed_loop()`: gaze -> perceive -> plan -> act, no host round trip); `gaze='LookAhead'` / `'LookGoal'`
               (yaw_planner.py:18-39 / :225-257) and `gaze='Owl'` (:151-222) run on the device the same way on a backend
               that has them
+  'Jerk_Primitive' with `device_plugins=True`: traj_planner.py:403-516 runs on the device between the two halves of the step
+              (include/d2d_jerk.h, one launch of libd2d_jerk.so that writes plan_ok / wp_valid / wp; the planner mode stays
+              'external').  `step`, `perceive` / `act`, `rollout` and `reset` run it; `closed_loop` does not (the persistent
+              kernel cannot take a stage from another library).  gaze: 'external' / None (the caller's actions), 'Rotating',
+              'NoControl'
 
 Motion profiles (`params.motion_profile`)
   'CVM'       the agents move with their preferred velocity, inside the fused step (D2D_ST_AGENTS)
@@ -217,7 +222,9 @@ def _grid_tile(params, backend, grid_layout):
 
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
-                 kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None):
+                 kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None):
+        """`jerk_tie`: (tie_perm, tie_eq) for planner='Jerk_Primitive' in place of the table of this host's np.argsort
+        (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it."""
         self.params = with_defaults(params)
         self.num_envs = int(num_envs)
         self.env_offset = int(env_offset)
@@ -289,7 +296,24 @@ class VecDrone2DEnv:
                 st.rng = st.rng_draws = None
         self.reward = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)   # drone_v2.py:257
         self.plugins = None
-        if device_plugins:
+        self.jerk = None
+        if device_plugins and planner == 'Jerk_Primitive':
+            # its own library and its own per-batch state (jerk_plugin.JerkState): no d2d_plan is involved
+            if gaze not in ('external', None, 'Rotating', 'NoControl'):
+                raise NotImplementedError(f"device plugins: planner 'Jerk_Primitive' / gaze {gaze!r}: the device Jerk_Primitive planner "
+                                          "takes gaze 'external' (the caller's actions), 'Rotating' or 'NoControl'; drive any other "
+                                          'policy from the host (gaze.LookAhead, ...) and pass its actions to step()')
+            backend_for(backend, device, 'supports_jerk', "has no Jerk_Primitive planner (planner='Jerk_Primitive' with "
+                        'device_plugins=True runs on the HIP backend)')
+            if not kf_enabled and N:
+                raise ValueError("device plugins: planner 'Jerk_Primitive' reads the Kalman trackers (kf_enabled=True)")
+            from .jerk_plugin import JerkState
+            self.jerk = JerkState(self.params, self.cfg, self.device, self.tracker_radius.numpy() if N and self.num_envs else None,
+                                  tie=jerk_tie)
+            self._jerk_call = self.jerk.call(self.state)
+            if gaze in ('Rotating', 'NoControl'):
+                self.state.action.fill_(1.0 if gaze == 'Rotating' else 0.0)
+        elif device_plugins:
             from .device_plugins import PluginState
             gaze = gaze if gaze is not None else self.params.gaze_method
             if planner not in ('Primitive', 'NoMove') or gaze not in ('Oxford', 'LookAhead', 'LookGoal', 'Owl', 'Rotating', 'NoControl',
@@ -348,11 +372,30 @@ class VecDrone2DEnv:
     def run_step(self):
         """d2d_step with the action already set; under RVO the agents move first, then every other stage (the state machine stage,
         which d2d_step runs before the agents, does not touch them: the order is the reference's)"""
-        if self.rvo:
+        if self.jerk is not None:
+            self.run_perceive()
+            self.run_jerk_plan()
+            self.backend.act(self.cfg, self._st)
+        elif self.rvo:
             self._rvo_agents()
             self.backend.run_stages(self.cfg, self._st, A.ST_ALL & ~A.ST_AGENTS)
         else:
             self.backend.step(self.cfg, self._st)
+
+    def run_jerk_plan(self):
+        """d2d_jerk_plan for every env: plan_ok / wp_valid / wp of this step, from what d2d_perceive left"""
+        if self.num_envs:
+            self.backend.jerk_plan(self._jerk_call)
+
+    @property
+    def jerk_choice(self):
+        """[B] int32: the heading index (theta / 5) the latest plan chose, -1 where it failed"""
+        return self.jerk.t['choice']
+
+    @property
+    def jerk_stat(self):
+        """[B] int32: include/d2d_jerk.h D2D_JERK_STAT_*"""
+        return self.jerk.t['stat']
 
     def run_perceive(self, stages=A.ST_PERCEIVE):
         """d2d_perceive, or the stages of it named; the agents stage is the RVO launches under RVO"""
@@ -400,8 +443,11 @@ class VecDrone2DEnv:
         return self._result()
 
     def perceive(self):
-        """First half of step() (lines 153-187); a host planner plugin runs after this."""
+        """First half of step() (lines 153-187); a host planner plugin runs after this (the device Jerk_Primitive planner runs
+        here, as the last part of this half)."""
         self.run_perceive()
+        if self.jerk is not None:
+            self.run_jerk_plan()
 
     def act(self, actions):
         """Second half of step() (lines 198-255)."""
@@ -421,8 +467,8 @@ class VecDrone2DEnv:
         if pin is not None:
             pin = torch.as_tensor(pin, dtype=torch.float64, device=self.device).contiguous()
         coll = torch.empty((T, self.num_envs), dtype=torch.uint8, device=self.device) if collisions else None
-        if self.rvo:
-            # a host loop of the RVO step (`streams` is ignored): pin = a copy into the drone record before each step, collisions =
+        if self.rvo or self.jerk is not None:
+            # a host loop of the RVO step (and of the Jerk_Primitive step, whose plan is a launch of another library) (`streams` is ignored): pin = a copy into the drone record before each step, collisions =
             # a copy of the flag after it, as d2d_rollout does them
             # With a [rows, B, N, 2] block of draws step t of the run takes row (row0 + t) % rows, as d2d_rollout does.  A single
             # d2d_run_stages reads the block's first row whatever noise_row0 says, so each step is handed its own row.
@@ -504,6 +550,10 @@ class VecDrone2DEnv:
         Primitive.replan_check + plan; act (experiment.py:68-70).  `auto_reset`: an env whose episode ended restarts
         from its seeded world with fresh plugin state at its next step.  `freeze_done`: an env whose episode ended
         stays as it ended (one episode per env; `episode_stats()` then holds one CSV row per env)."""
+        if self.jerk is not None:
+            raise NotImplementedError("closed_loop(): planner 'Jerk_Primitive' does not run inside the persistent closed loop (its "
+                                      'stage lives in libd2d_jerk.so); step the env with step() / perceive() + act(), or run '
+                                      'episodes through runner.Experiment')
         if self.plugins is None:
             raise RuntimeError('closed_loop() needs device_plugins=True')
         if self.rvo:
@@ -521,6 +571,10 @@ class VecDrone2DEnv:
             if mask is not None:
                 mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             self.backend.plan_reset(self.cfg, self._plan, mask, 1)
+        if self.jerk is not None and self.num_envs and self.cfg.N:
+            if mask is not None:
+                mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            self.backend.jerk_reset(self.jerk.t['trk_radius'], self.jerk.t['trk_prev'], self.jerk.trk_radius0, mask, 1)
 
     def sync(self):
         self.backend.sync()
