@@ -2054,10 +2054,8 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
 // rematerialise, and past ~100 of them it spills to VGPR lanes (v_readlane on every use).  Overwriting the
 // kernel's own copy of the config with the literals the host has verified turns them into immediates:
 // constant-folded tile sizes and LDS offsets, no spills.  Any other config takes the generic instantiation.
-// SPEC 1: N <= 16 agent slots, SPEC 2: N <= 40 (the default map plus the 14 obstacle_map agents, the reference's sweeps of up
-// to 30 agents; 40 is where both grids whole + the agent planes still leave four workgroups per CU in every phase), SPEC 3: the
-// default geometry with any N (LDS capacity and waves per workgroup stay run-time values)
-__host__ __device__ constexpr int spec_ncap(int spec) { return spec == 1 ? 16 : (spec == 2 ? 40 : 0); }
+// (spec_ncap, the agent slots of SPEC 1 / 2 / 3, and the match / apply pairs: d2d_plan_spec.h)
+#include "d2d_plan_spec.h"
 // Both grids staged whole in LDS (Geom.full) only for the instantiation with few agents (N <= 16: the per-wave working set
 // then stays below 10 KB, four 4-wave workgroups per CU).  With more agents the per-agent planes already fill the LDS and
 // 5 KB more per wave cost occupancy in the persistent loop -- measured on BASELINE config 4 (24 agents): 4.9e7 env-steps/s
@@ -2073,21 +2071,6 @@ __host__ __device__ constexpr bool spec_tiled(int spec) { return spec == 4; }
 __host__ __device__ constexpr bool spec_generic(int spec) { return spec == 0 || spec == 4; }
 // ray candidates culled against the cone of the rays (ray_cull<true>): where an env has enough agents for it to pay
 __host__ __device__ constexpr bool spec_cone(int spec) { return spec != 1; }
-__host__ __device__ inline bool spec_default_matches(const d2d_cfg &c) {
-  return c.W == 50 && c.H == 50 && c.R == 50 && c.L == 33 && c.dt == 0.1 && c.scale == 10.0 &&
-         c.W_px == 500.0 && c.H_px == 500.0 && c.ray_off0 == -0x1.921fb54442d18p-1 && c.ray_dth == 0x1.015bf9217271ap-5 &&
-         c.depth == 80.0 && c.drone_radius == 10.0 && c.yaw_rate == 80.0 && c.max_acc == 40.0 && c.max_steps == 800.0 &&
-         c.sigma == 0.0 && c.grid_tile == 0;
-}
-
-__device__ __forceinline__ void spec_default_apply(d2d_cfg &c) {
-  c.W = 50; c.H = 50; c.R = 50; c.L = 33;
-  c.dt = 0.1; c.scale = 10.0; c.W_px = 500.0; c.H_px = 500.0;
-  c.ray_off0 = -0x1.921fb54442d18p-1; c.ray_dth = 0x1.015bf9217271ap-5;
-  c.depth = 80.0; c.drone_radius = 10.0; c.yaw_rate = 80.0; c.max_acc = 40.0; c.max_steps = 800.0; c.sigma = 0.0;
-  c.grid_tile = 0;
-}
-
 extern __shared__ __attribute__((aligned(16))) char d2d_lds[];
 
 // The kernel's own argument block as it lies in the kernarg segment (constant memory).  The generic kernel reads the
@@ -2316,6 +2299,22 @@ __device__ __forceinline__ PhaseIn phase_enter(const ClosedArgs *ap, int e_, int
   in.lane = lane;
   return in;
 }
+// The plan a phase works on.  PDEF false: the parked one, every scalar fetched through a scalar load where it is used.  PDEF true (the host
+// has verified plan_default_matches): the phase's own copy with the literals written over the matched scalars (plan_default_apply,
+// d2d_plan_spec.h), as spec_default_apply does for the geometry -- nu, n_sample, n_yaw, the thresholds and the dispatch on planner /
+// gaze are immediates, the divisions by nu / n_sample shifts, an expansion one batch of 64 primitives.  Pointers, capacities and the
+// tables' contents stay what the parked plan holds.
+template <bool PDEF, typename F>
+__device__ __forceinline__ auto with_plan(ArgsPtr a, F f) {
+  if constexpr (PDEF) {
+    d2d_plan p = a->p;
+    plan_default_apply(p);
+    return f(p);
+  } else {
+    return f(a->p);
+  }
+}
+
 // Round 4: EVERY phase is inlined into the persistent kernel (a kernel has no callee-saved registers: as functions the phases saved
 // and restored up to 48 VGPRs per call -- 11 KB of scratch written and read per env-step in the gaze + perceive phase of the
 // many-agent kernels, 12 KB per search).  Two things make that work where rounds 1-3 measured spills: the laundering above, and
@@ -2326,7 +2325,7 @@ __device__ __forceinline__ PhaseIn phase_enter(const ClosedArgs *ap, int e_, int
 
 // The planner stage as two calls: the part every step runs (small: few registers to save), and the search, called
 // only when the trajectory is empty (a few percent of the steps).
-template <int SPEC>
+template <int SPEC, bool PDEF>
 __device__ __forceinline__ int ph_plan_quick(const ClosedArgs *ap, int e_, int lds_off_) {
   const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
@@ -2338,7 +2337,7 @@ __device__ __forceinline__ int ph_plan_quick(const ClosedArgs *ap, int e_, int l
     constexpr int cap = spec_ncap(SPEC);
     __builtin_assume(c.N <= cap);
   }
-  const bool need = plan_env_quick(c, a->s, a->p, e, lane, base);
+  const bool need = with_plan<PDEF>(a, [&](const d2d_plan &p) __attribute__((always_inline)) { return plan_env_quick(c, a->s, p, e, lane, base); });
   wave_sync_global();
   return need ? 1 : 0;
 }
@@ -2351,7 +2350,7 @@ __device__ __forceinline__ int ph_plan_quick(const ClosedArgs *ap, int e_, int l
 // value of the search is loop-invariant in the caller's step loop: hoisted out of it, such values stay live across the other
 // phases' calls and spill.  Same-call A/B against the called form: config 2 +3 % (600 / 300 and the driver's 20-step window),
 // config 3 +4 %, config 4 +2.4 %.
-template <int SPEC>
+template <int SPEC, bool PDEF>
 __device__ __forceinline__ void ph_plan_search(const ClosedArgs *ap, int e_, int lds_off_) {
   const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
@@ -2363,7 +2362,7 @@ __device__ __forceinline__ void ph_plan_search(const ClosedArgs *ap, int e_, int
     constexpr int cap = spec_ncap(SPEC);
     __builtin_assume(c.N <= cap);
   }
-  plan_env_search(c, a->s, a->p, e, lane, base);
+  with_plan<PDEF>(a, [&](const d2d_plan &p) __attribute__((always_inline)) { plan_env_search<PDEF>(c, a->s, p, e, lane, base); });
   wave_sync_global();
 }
 
@@ -2373,7 +2372,7 @@ __device__ __forceinline__ void ph_plan_search(const ClosedArgs *ap, int e_, int
 // ph_plan_search and then ph_stages<ACT>), else the episode flag the collision stage wrote.
 // `walls_ok`: the env's "every remaining waypoint passed the wall test and only rays have written the map since" flag
 // (plan_env_quick), carried by the caller across the steps of a launch.
-template <int SPEC>
+template <int SPEC, bool PDEF>
 __device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds_off_, int &walls_ok) {
   const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
@@ -2388,7 +2387,7 @@ __device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds
   double4 w_head;
   int wk = __builtin_amdgcn_readfirstlane(walls_ok);
   asm volatile("; phase" : "+s"(wk));
-  const bool need = plan_env_quick(c, a->s, a->p, e, lane, base, &w_head, &wk);
+  const bool need = with_plan<PDEF>(a, [&](const d2d_plan &p) __attribute__((always_inline)) { return plan_env_quick(c, a->s, p, e, lane, base, &w_head, &wk); });
   walls_ok = __builtin_amdgcn_readfirstlane(wk);
   if (need) {
     wave_sync_global();
@@ -2415,7 +2414,7 @@ __device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds
 // gaze + the stages that follow it in one call (one set of callee-saved registers, one fence fewer per step)
 // `done_`: the env's episode flag as the caller knows it (the act phase of the step before returns it) -- no load, no round trip,
 // before the gaze stage can ask for anything else.  Returns the flag as this call's collision stage wrote it (-1: it did not run).
-template <int SPEC, uint32_t STAGES>
+template <int SPEC, bool PDEF, uint32_t STAGES>
 __device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_off_, int t_, int done_) {
   const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
@@ -2428,7 +2427,9 @@ __device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int 
 #ifdef D2D_CHAIN_PROF
   const unsigned long long pp0 = __builtin_amdgcn_s_memtime();
 #endif
-  gaze_env<true>(c, a->s, a->p, a->init, a->on_done == D2D_DONE_RESET, e, lane, base, known_done);
+  with_plan<PDEF>(a, [&](const d2d_plan &p) __attribute__((always_inline)) {
+    gaze_env<true, PDEF>(c, a->s, p, a->init, a->on_done == D2D_DONE_RESET, e, lane, base, known_done);
+  });
   wave_sync_global();
 #ifdef D2D_CHAIN_PROF
   D2D_PHASE_ADD(0, pp0);
@@ -2470,16 +2471,26 @@ __device__ __forceinline__ int ph_stages(const ClosedArgs *ap, int e_, int lds_o
   return r.done;
 }
 
-template <int SPEC>
+template <int SPEC, bool PDEF = false>
 __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed(const ClosedArgs *__restrict__ a) {
+  static_assert(!PDEF || SPEC == 1, "the plan's defaults are folded into the few-agent kernel of the default geometry only");
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   const int wpb = (int)(blockDim.x / WAVE);
   const int e = blockIdx.x * wpb + wv;
   if (e >= a->c.B) return;
   d2d_cfg c = a->c;
   if (!spec_generic(SPEC)) spec_default_apply(c);
-  const int off = wv * closed_wave_bytes<SPEC>(c, a->p, wpb);
-  const bool split = a->p.planner == D2D_PLAN_PRIMITIVE;
+  int off;
+  bool split;
+  if constexpr (PDEF) {
+    d2d_plan p = a->p;
+    plan_default_apply(p);
+    off = wv * closed_wave_bytes<SPEC>(c, p, wpb);
+    split = p.planner == D2D_PLAN_PRIMITIVE;
+  } else {
+    off = wv * closed_wave_bytes<SPEC>(c, a->p, wpb);
+    split = a->p.planner == D2D_PLAN_PRIMITIVE;
+  }
   const int nsteps = a->nsteps;
   const bool freeze = a->on_done == D2D_DONE_FREEZE;
   int nsearch = 0;
@@ -2501,12 +2512,12 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
       // latency-bound, so the three waves it shares the SIMD with give up little.  (+4 % at 4096 envs; thresholds 16-64
       // and levels 1-2 measure the same, level 3 -- the search's own -- less.)
       if (nsearch * 32 > t + 16) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
-      ph_gaze_stages<SPEC, D2D_ST_PERCEIVE>(a, e, off, t, flag_done);
+      ph_gaze_stages<SPEC, PDEF, D2D_ST_PERCEIVE>(a, e, off, t, flag_done);
 #ifdef D2D_CHAIN_PROF
       const unsigned long long q0 = __builtin_amdgcn_s_memtime();
 #endif
       // the planner's every-step part and, unless it has to search, the act phase behind it in the same call (ph_plan_act)
-      const int pa = __builtin_amdgcn_readfirstlane(ph_plan_act<SPEC>(a, e, off, walls_ok));
+      const int pa = __builtin_amdgcn_readfirstlane(ph_plan_act<SPEC, PDEF>(a, e, off, walls_ok));
 #ifdef D2D_CHAIN_PROF
       D2D_PHASE_ADD(2, q0);  // (planner every-step part + act of the steps without a search)
 #endif
@@ -2514,7 +2525,7 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
 #ifdef D2D_CHAIN_PROF
         const unsigned long long s0 = __builtin_amdgcn_s_memtime();
 #endif
-        ph_plan_search<SPEC>(a, e, off);
+        ph_plan_search<SPEC, PDEF>(a, e, off);
         nsearch += 1;
         walls_ok = 0;  // a new trajectory (or none): its waypoints have not been through replan_check yet
 #ifdef D2D_CHAIN_PROF
@@ -2530,7 +2541,7 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
         flag_done = pa;
       }
     } else {
-      flag_done = __builtin_amdgcn_readfirstlane(ph_gaze_stages<SPEC, D2D_ST_ALL>(a, e, off, t, flag_done));
+      flag_done = __builtin_amdgcn_readfirstlane(ph_gaze_stages<SPEC, PDEF, D2D_ST_ALL>(a, e, off, t, flag_done));
     }
   }
 #ifdef D2D_CHAIN_PROF
@@ -2584,7 +2595,8 @@ int spec_of(const d2d_cfg &c) {
 // has held them since there were five, so that its bytes do not depend on the dispatch below.
 [[maybe_unused]] const void *const kInstantiationOrder[] = {
     (const void *)k_stages<3>, (const void *)k_stages<1>, (const void *)k_stages<2>, (const void *)k_stages<4>, (const void *)k_stages<0>,
-    (const void *)k_closed<0>, (const void *)k_closed<4>, (const void *)k_closed<3>, (const void *)k_closed<1>, (const void *)k_closed<2>};
+    (const void *)k_closed<0>, (const void *)k_closed<4>, (const void *)k_closed<3>, (const void *)k_closed<1>, (const void *)k_closed<2>,
+    (const void *)k_closed<1, true>};
 
 // f(IntC<spec>{}): the run-time `spec` as a compile-time constant
 template <typename F>
@@ -2925,11 +2937,16 @@ int d2d_closed_loop(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, int
       ClosedArgs *dev = (ClosedArgs *)p->launch_args;
       hipLaunchKernelGGL(k_closed_args, dim3(1), dim3(64), 0, (hipStream_t)stream, dev, *c, *s, *p, auto_reset ? *init : *s,
                          (int)on_done, (int)nsteps);
-      with_spec(l.spec, [&](auto S) {
-        constexpr int SPEC = decltype(S)::value;
-        lds_optin(k_closed<SPEC>, l.lds());
-        hipLaunchKernelGGL(k_closed<SPEC>, env_grid(c->B, l.wpb), env_block(l.wpb), l.lds(), (hipStream_t)stream, (const ClosedArgs *)dev);
-      });
+      auto launch = [&](auto kernel) {
+        lds_optin(kernel, l.lds());
+        hipLaunchKernelGGL(kernel, env_grid(c->B, l.wpb), env_block(l.wpb), l.lds(), (hipStream_t)stream, (const ClosedArgs *)dev);
+      };
+      // the plugins' default parameters folded into the kernel (k_closed<1, true>) where the plan holds exactly them; D2D_PLAN_FOLD=0 in
+      // the environment, read at every call, keeps such a plan on k_closed<1> (same-process A/B, tests/test_gpu_plan_fold.py)
+      const char *fold_env = getenv("D2D_PLAN_FOLD");
+      const bool fold_off = fold_env && fold_env[0] == '0' && fold_env[1] == '\0';
+      if (l.spec == 1 && !fold_off && plan_default_matches(*c, *p)) launch(k_closed<1, true>);
+      else with_spec(l.spec, [&](auto S) { launch(k_closed<decltype(S)::value>); });
       return launched();
     }
   }

@@ -306,6 +306,10 @@ __host__ __device__ inline bool search_wall_rows(int W, int H) { return W <= 64 
 // Primitive.plan's search (traj_planner.py:128-218) by one wave.  Returns the number of waypoints written, -1 = failure.
 // 0 is a success: the start node is the goal node (target within the search threshold of the start), the reference
 // returns True with an empty trajectory (traj_planner.py:158-160, 204-216).
+// PDEF: `p` holds the default parameters as literals (plan_default_apply, d2d_plan_spec.h; the persistent kernel k_closed<1, true>) --
+// nu = n_sample = 8: 64 primitives = one batch per expansion, and the (x_acc, y_acc) / (primitive, sample) indices are shifts.  The same
+// integers as FastDiv's for every index below 2^24; no floating-point expression changes.
+template <bool PDEF = false>
 __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, int e, int lane, const TrkView &T,
                            const SearchLds &S, const unsigned char *__restrict__ dm, double inv_scale) {
   const double H = p.horizon;
@@ -462,7 +466,8 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
   int nn = 1, open_n = 1, goal = -1, itr = 0, expansions = 0;
   bool overflow = false;
   bool lds_dict = true;  // the dict lives in LDS (S.lh); false once the search has outgrown it: then in `tab`
-  const int nprim = p.nu * p.nu;
+  const int nprim = PDEF ? 64 : p.nu * p.nu;
+  static_assert(WAVE == 64, "PDEF: one expansion = one batch of 64 primitives");
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
   const FastDiv fd_nu(p.nu), fd_ns(p.n_sample);
   // |sample| <= |p| + T |v| + T^2 |a| / 2 for every sample time T < horizon: one bound per expansion instead of a test per sample
@@ -563,7 +568,12 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
         ay = ay1;
       } else {
         int ia, ja;
-        fd_nu.divmod(ok ? pi : 0, ia, ja);  // no integer divisions in the loop: ~25 instructions each
+        if constexpr (PDEF) {
+          ia = pi >> 3;
+          ja = pi & 7;
+        } else {
+          fd_nu.divmod(ok ? pi : 0, ia, ja);  // no integer divisions in the loop: ~25 instructions each
+        }
         ax = S.us[ia];
         ay = S.us[ja];
       }
@@ -672,7 +682,12 @@ __device__ int plan_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan 
           for (int u = 0; u < NR; ++u) {
             const int q = q0 + u * WAVE + lane;
             in[u] = q < npair;
-            fd_ns.divmod(in[u] ? q : 0, pr[u], si[u]);
+            if constexpr (PDEF) {
+              pr[u] = in[u] ? q >> 3 : 0;
+              si[u] = in[u] ? q & 7 : 0;
+            } else {
+              fd_ns.divmod(in[u] ? q : 0, pr[u], si[u]);
+            }
           }
           double shx[NR], shy[NR], tt[NR], tt2[NR];
 #pragma unroll
@@ -1207,6 +1222,7 @@ __device__ __forceinline__ bool plan_env_quick(const d2d_cfg &c, const d2d_state
 }
 
 // Primitive.plan's search (traj_planner.py:125-218) for an env whose plan_env_quick returned true.
+template <bool PDEF = false>
 __device__ __forceinline__ void plan_env_search(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, int e, int lane, char *base) {
   TrkView T;
   SearchLds S;
@@ -1218,7 +1234,7 @@ __device__ __forceinline__ void plan_env_search(const d2d_cfg &c, const d2d_stat
   // spends its time on; its wave shares the SIMD with three others that mostly run throughput phases.  Raised issue
   // priority lets it go first whenever it is ready (0.78 ms -> its stand-alone 0.46 ms is the range at stake).
   __builtin_amdgcn_s_setprio(3);
-  const int found = plan_search(c, s, p, e, lane, T, S, dm, inv_scale);
+  const int found = plan_search<PDEF>(c, s, p, e, lane, T, S, dm, inv_scale);
   __builtin_amdgcn_s_setprio(0);
   wave_sync_global();
   plan_emit(s, p, e, lane, 0, found > 0 ? found : 0, found >= 0 ? 1 : 0);
@@ -1570,12 +1586,15 @@ __device__ __forceinline__ void owl_gaze_env(const d2d_cfg &c, const d2d_state &
 // cells fetched before the first is used, the pairwise plan staged in LDS.
 // `known_done`: the env's episode flag where the caller holds it (the persistent loop), -1: read here.
 // OWL: whether the caller's kernel carries the Owl stage (k_gaze does not: the stage has k_gaze_owl).
-template <bool OWL>
+// PDEF: `p` holds the default parameters as literals (plan_default_apply, d2d_plan_spec.h; the persistent kernel k_closed<1, true>): six
+// candidates, so the per-cell passes carry six accumulators and no `a < n_yaw` test (the seventh's view bit is never set: its sums are +0.0).
+template <bool OWL, bool PDEF = false>
 __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, const d2d_plan &p, const d2d_state &init,
                                          int auto_reset, int e, int lane, char *base, int known_done = -1, bool reset_rng = true) {
   // ---- one batch of loads: everything the stage needs that does not hang on another load (the episode flag, the pose, the step
   //      count, the trajectory header, the table heads, the pairwise plan, the candidates' yaw rates) is requested before the first
   //      of them is looked at -- one round trip where the straightforward order makes seven dependent ones ----
+  constexpr int NA = PDEF ? 6 : 7;  // candidates the per-cell passes carry (n_yaw <= 7: plan_check)
   const bool oxford = p.gaze == D2D_GAZE_OXFORD;
   const GazeGeom g = gaze_geom(c, p);
   const double *dr = s.drone + (size_t)e * D2D_DF;
@@ -1820,7 +1839,9 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
 #endif
   GZ(3);  // live-cell compaction
 #ifndef D2D_GAZE_EXACT_ONLY
-  double qa[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // this lane's part of every candidate's sum, in ANY order (the quick decision below)
+  double qa[NA];  // this lane's part of every candidate's sum, in ANY order (the quick decision below)
+#pragma unroll
+  for (int a = 0; a < NA; ++a) qa[a] = 0.0;
 #endif
   bool any_hot = false;  // this lane has met a cell that adds a non-zero term to some candidate's sum
   for (int l0 = 0; l0 < nlive; l0 += 4 * WAVE) {
@@ -1869,7 +1890,7 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
           const double dxv = x - hx, dyv = y - hy;
           const double rhs = quick * d2, hi = rhs * (1.0 + 1e-12), lo = rhs * (1.0 - 1e-12), top = d2 * (1.0 - 1e-12);
 #pragma unroll
-          for (int a = 0; a < 7; ++a) {
+          for (int a = 0; a < NA; ++a) {
             if (a < p.n_yaw) {
               const double dot = dxv * vdir[2 * a] + dyv * vdir[2 * a + 1];
               // dot^2 with dot's sign (hi, lo, top are > 0): `dot > 0 and dot^2 > hi` is `sq > hi`, `dot <= 0 or dot^2 < lo` is `sq < lo`
@@ -1900,7 +1921,7 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
         {
           const int hbits = hot ? (int)bits : 0;
 #pragma unroll
-          for (int a = 0; a < 7; ++a) {  // + view * reward, view in {0.0, 1.0} (as in the block sums below)
+          for (int a = 0; a < NA; ++a) {  // + view * reward, view in {0.0, 1.0} (as in the block sums below)
             const double view = __hiloint2double(((hbits << (31 - a)) >> 31) & 0x3ff00000, 0);
             qa[a] = __builtin_fma(rw, view, qa[a]);
           }
@@ -1945,7 +1966,7 @@ __device__ __forceinline__ void gaze_env(const d2d_cfg &c, const d2d_state &s, c
     double *qs = stk;  // [8]: the view directions kept there have been consumed by the reward pass
     if (lane < 8) qs[lane] = 0.0;
 #pragma unroll
-    for (int a = 0; a < 7; ++a)
+    for (int a = 0; a < NA; ++a)
       if (qa[a] != 0.0) atomicAdd(&qs[a], qa[a]);  // (LDS operations of one wave execute in order: behind the clear above)
     wave_sync_lds();
     const double q_l = qs[min(lane, 7)];

@@ -54,12 +54,8 @@ def classify(op):
     return 'other'
 
 
-def main():
-    lib = os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc', 'libd2d_hip.so')
-    args = sys.argv[1:]
-    if args and args[0].endswith('.so'):
-        lib = args.pop(0)
-    filt = args
+def disassemble(lib):
+    """(disassembly, ELF notes) of the gfx950 code object embedded in `lib`"""
     tmp = tempfile.mkdtemp(prefix='isa_')
     try:
         local = os.path.join(tmp, 'lib.so')
@@ -73,6 +69,13 @@ def main():
         notes = subprocess.check_output([f'{LLVM}/llvm-readelf', '--notes', co], text=True)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+    return dis, notes
+
+
+def collect(lib):
+    """(funcs, meta): per function of the disassembly a Counter of instruction classes (+ '_total'); per kernel (mangled name) the
+    register / spill / scratch figures of its descriptor notes"""
+    dis, notes = disassemble(lib)
     # kernel metadata: name -> vgpr / sgpr / spills / scratch
     meta = {}
     cur = {}
@@ -111,6 +114,51 @@ def main():
         if m and name:
             funcs[name][classify(m.group(1))] += 1
             funcs[name]['_total'] += 1
+    return funcs, meta
+
+
+def regions(lib, kernel):
+    """The instruction stream of the kernel whose short name is `kernel`, cut at every s_memtime (a diagnostic build's clock stamps:
+    -DD2D_CHAIN_PROF -DD2D_SEARCH_PROF), in address order: one Counter per piece.  Blocks are laid out roughly in source order, so a
+    piece is roughly a stamped section -- a static figure to compare two builds by, not an exact one."""
+    dis, _ = disassemble(lib)
+    out, cur = [], None
+    for ln in dis.splitlines():
+        m = re.match(r'^[0-9a-f]+ <(.*)>:$', ln)
+        if m:
+            cur = None
+            if short_name(m.group(1)).replace('void ', '') == kernel:
+                cur = collections.Counter()
+                out.append(cur)
+            continue
+        m = re.match(r'^\s+([a-z_0-9]+)\b', ln)
+        if m and cur is not None:
+            if m.group(1).startswith('s_memtime'):
+                cur = collections.Counter()
+                out.append(cur)
+            cur[classify(m.group(1))] += 1
+            cur['_total'] += 1
+    return out
+
+
+def short_name(fn):
+    return re.sub(r'\(.*', '', re.sub(r'\(anonymous namespace\)::', '', fn))
+
+
+def demangle(n):
+    return short_name(subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip())
+
+
+VALU_CLASSES = ('v_f64', 'vcmp_f64', 'vcvt_f64', 'v_f32', 'v_int', 'v_mov', 'vcmp', 'vcvt', 'lane')
+
+
+def main():
+    lib = os.path.join(ROOT, 'gym-drone2d-activeperception_amd', 'csrc', 'libd2d_hip.so')
+    args = sys.argv[1:]
+    if args and args[0].endswith('.so'):
+        lib = args.pop(0)
+    filt = args
+    funcs, meta = collect(lib)
     cols = ['v_f64', 'vcmp_f64', 'vcvt_f64', 'v_f32', 'v_int', 'v_mov', 'vcmp', 'vcvt', 'lane', 'salu', 's_load', 's_wait', 's_branch',
             'lds', 'vmem', 'scratch']
     print(f'{"function":58s} {"total":>6s} {"VALU":>6s} ' + ' '.join(f'{c:>8s}' for c in cols))
@@ -119,15 +167,12 @@ def main():
             continue
         if filt and not any(f in fn for f in filt):
             continue
-        valu = sum(c[k] for k in ('v_f64', 'vcmp_f64', 'vcvt_f64', 'v_f32', 'v_int', 'v_mov', 'vcmp', 'vcvt', 'lane'))
-        short = re.sub(r'\(anonymous namespace\)::', '', fn)
-        short = re.sub(r'\(.*', '', short)[:58]
+        valu = sum(c[k] for k in VALU_CLASSES)
+        short = short_name(fn)[:58]
         print(f'{short:58s} {c["_total"]:6d} {valu:6d} ' + ' '.join(f'{c[k]:8d}' for k in cols))
     print()
     for n, m in meta.items():
-        dem = subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip()
-        dem = re.sub(r'\(anonymous namespace\)::', '', dem)
-        dem = re.sub(r'\(.*', '', dem)
+        dem = demangle(n)
         if filt and not any(f in dem for f in filt):
             continue
         print(f'{dem[:58]:58s} vgpr {m.get("vgpr_count", "?"):>4s} agpr {m.get("agpr_count", "?"):>3s} sgpr {m.get("sgpr_count", "?"):>4s} '
