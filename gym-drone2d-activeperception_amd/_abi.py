@@ -211,3 +211,30 @@ def bind_jerk(lib):
         'reset': (C.c_int, [V, V, V, V, I, I, I, V]),
     }
     return _bind(lib, 'd2d_jerk_', sig)
+
+
+# ---- include/d2d_gaze.h: the gaze decision of the step path on the device (csrc/gaze/libd2d_gaze.so, its own version) ----
+D2D_GAZE_VERSION = 1
+GAZE_K_LOOKAHEAD, GAZE_K_OWL = GAZE_LOOKAHEAD, GAZE_OWL
+GAZE_MAX_N = 1024
+GAZE_CALL_POINTERS = ('drone', 'target', 'active', 'kf', 'flags', 'owl_state', 'owl_tab', 'action')
+GAZE_CALL_INT_FIELDS = ('B', 'N', 'kind', 'reserved')
+GAZE_CALL_F64_FIELDS = ('dt', 'yaw_rate_max')
+
+
+class GazeCall(C.Structure):
+    """include/d2d_gaze.h `d2d_gaze_call`."""
+    _fields_ = [(n, C.c_void_p) for n in GAZE_CALL_POINTERS] + [(n, C.c_int32) for n in GAZE_CALL_INT_FIELDS] + \
+               [(n, C.c_double) for n in GAZE_CALL_F64_FIELDS]
+
+
+def bind_gaze(lib):
+    """argtypes / restypes of include/d2d_gaze.h on a loaded CDLL."""
+    V, I = C.c_void_p, C.c_int32
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'act': (C.c_int, [C.POINTER(GazeCall), V]),
+        'reset': (C.c_int, [V, V, I, I, V]),
+    }
+    return _bind(lib, 'd2d_gaze_', sig)

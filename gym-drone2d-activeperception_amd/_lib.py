@@ -11,6 +11,7 @@ WORLDS_LIB_PATH = os.path.join(_HERE, 'csrc', 'worlds', 'libd2d_worlds.so')     
 METRICS_LIB_PATH = os.path.join(_HERE, 'csrc', 'metrics', 'libd2d_metrics.so')          # include/d2d_metrics.h
 RVO_LIB_PATH = os.path.join(_HERE, 'csrc', 'rvo', 'libd2d_rvo.so')                      # include/d2d_rvo.h
 JERK_LIB_PATH = os.path.join(_HERE, 'csrc', 'jerk', 'libd2d_jerk.so')                   # include/d2d_jerk.h
+GAZE_LIB_PATH = os.path.join(_HERE, 'csrc', 'gaze', 'libd2d_gaze.so')                   # include/d2d_gaze.h
 
 
 class D2DError(RuntimeError):
@@ -35,6 +36,7 @@ _LIBRARIES = {
     'libd2d_metrics.so': (A.bind_metrics, 'version', 'D2D_METRICS_VERSION', 'version', 'metrics/build.sh'),
     'libd2d_rvo.so': (A.bind_rvo, 'version', 'D2D_RVO_VERSION', 'version', 'rvo/build.sh'),
     'libd2d_jerk.so': (A.bind_jerk, 'version', 'D2D_JERK_VERSION', 'version', 'jerk/build.sh'),
+    'libd2d_gaze.so': (A.bind_gaze, 'version', 'D2D_GAZE_VERSION', 'version', 'gaze/build.sh'),
 }
 
 
@@ -78,6 +80,11 @@ def load_jerk_library(path=JERK_LIB_PATH):
     return _load('libd2d_jerk.so', path)
 
 
+def load_gaze_library(path=GAZE_LIB_PATH):
+    """The step path's gaze decision, a library of its own (include/d2d_gaze.h)."""
+    return _load('libd2d_gaze.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -105,6 +112,7 @@ class HipBackend:
     supports_difficulty_tables = True     # include/d2d_metrics.h: the traversability and survival-fit metrics (metrics.py)
     supports_rvo = True                   # include/d2d_rvo.h: the RVO motion profile (VecDrone2DEnv with motion_profile='RVO')
     supports_jerk = True                  # include/d2d_jerk.h: the Jerk_Primitive planner (VecDrone2DEnv with planner='Jerk_Primitive')
+    supports_step_gaze = True             # include/d2d_gaze.h: LookAhead / Owl as a launch in front of the step (policy_step, run_episodes)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -117,6 +125,7 @@ class HipBackend:
         self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
         self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
         self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
+        self.glib = self.gfn = None       # libd2d_gaze.so: loaded by the first gaze call of the step path, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -255,6 +264,19 @@ class HipBackend:
         B, N = trk_radius.shape
         self._jerk('reset', trk_radius.data_ptr(), trk_prev.data_ptr(), trk_radius0.data_ptr(),
                    None if mask is None else mask.data_ptr(), int(mask_stride), B, N)
+
+    def _gaze(self, name, *args):
+        if self.gfn is None:
+            self.glib, self.gfn = load_gaze_library()
+        _check(self.gfn[name](*args, self._stream()), self.gfn, 'd2d_gaze')
+
+    def gaze_act(self, call):
+        """d2d_gaze_act: `call` is an _abi.GazeCall of device pointers (gaze_plugin.GazeState.call)"""
+        self._gaze('act', C.byref(call))
+
+    def gaze_reset(self, owl_state, mask=None, mask_stride=1):
+        """d2d_gaze_reset: owl_state [B, OWL_STATE_F] float64 <- 0, for the envs of mask (or all)"""
+        self._gaze('reset', owl_state.data_ptr(), None if mask is None else mask.data_ptr(), int(mask_stride), owl_state.shape[0])
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

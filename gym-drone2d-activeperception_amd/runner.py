@@ -60,7 +60,44 @@ class Experiment:
         return row
 
 
-class ExperimentBatch:
+def batch_rows(params, env):
+    """One tuple per env of VecDrone2DEnv `env` with the columns of experiment.py:73-103, read off the state as its episodes left it."""
+    p, s = params, env.state
+    c = s.counters.cpu().numpy()
+    f = s.flags.cpu().numpy()
+    disc = (s.dmap != 0).flatten(1).sum(1).cpu().numpy()
+    out = []
+    for e in range(env.num_envs):
+        n = int(c[e, A.C_BUF_N])
+        tracking_time = float(c[e, A.C_BUF_TS]) * 0.1
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean_time = np.float64(tracking_time) / n if n else float('nan')
+        sm = int(c[e, A.C_SM])
+        out.append((p.gaze_method, p.planner, p.motion_profile, p.map_id + env.env_offset + e, p.agent_radius,
+                    p.agent_number, p.pillar_number, p.agent_max_speed, p.drone_max_speed, p.var_cam, p.init_position,
+                    p.target_list[0], int(c[e, A.C_STEPS]) * p.dt, int(disc[e]), n, mean_time,
+                    1 if sm == A.SM_GOAL_REACHED else 0, 1 if f[e, 0] == 1 else 0, 1 if f[e, 0] == 2 else 0,
+                    int(f[e, 2]), int(f[e, 1]), sm))
+    return out
+
+
+class _BatchRows:
+    """rows() / write_csv() of a batch whose envs have played one episode each (self.params, self.env)."""
+
+    def rows(self):
+        """One tuple per env with the columns of experiment.py:73-103."""
+        return batch_rows(self.params, self.env)
+
+    def write_csv(self, path):
+        new = not os.path.isfile(path)
+        with open(path, 'a', newline='') as fh:
+            w = csv.writer(fh)
+            if new:
+                w.writerow(CSV_COLUMNS)
+            w.writerows(self.rows())
+
+
+class ExperimentBatch(_BatchRows):
     """The reference's sweep of episodes (`main.py:26-57`: the same cfg over many map ids, one Experiment and one
     CSV row each) as ONE device batch: env i is the world of `map_id + i`, the gaze policy and the planner run on
     the device (Oxford / LookAhead / LookGoal / Owl / Primitive), every env plays exactly one episode (`D2D_DONE_FREEZE`)
@@ -83,7 +120,8 @@ class ExperimentBatch:
         if p.planner == 'Jerk_Primitive':
             raise NotImplementedError("ExperimentBatch: planner 'Jerk_Primitive' does not run inside the persistent closed loop (its "
                                       'stage lives in libd2d_jerk.so); step a VecDrone2DEnv(..., planner=\'Jerk_Primitive\', '
-                                      'device_plugins=True) with step(), or run the episodes through runner.Experiment, one at a time')
+                                      'device_plugins=True) with step(), or run the episodes through runner.Experiment, one at a time.  '
+                                      'runner.SteppedExperimentBatch plays the episodes of this planner as a batch')
         if p.gaze_method not in ('Oxford', 'Rotating', 'NoControl', 'LookAhead', 'LookGoal', 'Owl') or p.planner not in ('Primitive', 'NoMove'):
             raise NotImplementedError('ExperimentBatch runs the device plugins: gaze_method Oxford / LookAhead / LookGoal / Owl / '
                                       'Rotating / NoControl, planner Primitive / NoMove (use Experiment, one episode at a time, for '
@@ -135,30 +173,45 @@ class ExperimentBatch:
         self.env.sync()
         return self.rows()
 
-    def rows(self):
-        """One tuple per env with the columns of experiment.py:73-103."""
-        p, s = self.params, self.env.state
-        c = s.counters.cpu().numpy()
-        f = s.flags.cpu().numpy()
-        disc = (s.dmap != 0).flatten(1).sum(1).cpu().numpy()
-        out = []
-        for e in range(self.env.num_envs):
-            n = int(c[e, A.C_BUF_N])
-            tracking_time = float(c[e, A.C_BUF_TS]) * 0.1
-            with np.errstate(divide='ignore', invalid='ignore'):
-                mean_time = np.float64(tracking_time) / n if n else float('nan')
-            sm = int(c[e, A.C_SM])
-            out.append((p.gaze_method, p.planner, p.motion_profile, p.map_id + self.env.env_offset + e, p.agent_radius,
-                        p.agent_number, p.pillar_number, p.agent_max_speed, p.drone_max_speed, p.var_cam, p.init_position,
-                        p.target_list[0], int(c[e, A.C_STEPS]) * p.dt, int(disc[e]), n, mean_time,
-                        1 if sm == A.SM_GOAL_REACHED else 0, 1 if f[e, 0] == 1 else 0, 1 if f[e, 0] == 2 else 0,
-                        int(f[e, 2]), int(f[e, 1]), sm))
-        return out
 
-    def write_csv(self, path):
-        new = not os.path.isfile(path)
-        with open(path, 'a', newline='') as fh:
-            w = csv.writer(fh)
-            if new:
-                w.writerow(CSV_COLUMNS)
-            w.writerows(self.rows())
+STEPPED_GAZE_METHODS = ('LookAhead', 'Owl', 'LookGoal', 'Oxford', 'Rotating', 'NoControl')
+
+
+class SteppedExperimentBatch(_BatchRows):
+    """ExperimentBatch for `planner='Jerk_Primitive'`: the `Jerk_Primitive` half of the reference's validation sweeps
+    (script/validation_shape.py, validation_speed.py: planners x gaze methods x map ids) as device batches.  Env i is the world of
+    `map_id + i`; every env plays exactly one episode and `rows()` returns the reference's CSV rows.
+
+    The planner's stage lives in a library of its own, so the episodes do not run inside the persistent closed loop but over
+    `VecDrone2DEnv.run_episodes`: per step the gaze launch (include/d2d_gaze.h), the RVO launches under `motion_profile='RVO'`, the
+    first half of the step, the plan (include/d2d_jerk.h), the second half; finished envs are frozen (D2D_ST_SKIP_DONE) and the host
+    looks at the flags once every `check_every` steps.  Every `--gaze_method` name runs: LookAhead and Owl as that launch, Rotating
+    and NoControl as constants, and LookGoal and Oxford as the constant 0 they are under this planner (its trajectory is empty at
+    every policy call; Oxford's own maps are therefore not kept).  What a finished env still rewrites (the plan's outputs and tracker
+    bookkeeping; under RVO its agents) is nothing a row reads.  `jerk_tie`: as in VecDrone2DEnv."""
+
+    def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_worlds=False, jerk_tie=None):
+        from .vec_env import VecDrone2DEnv, build_worlds
+        from ._lib import HipBackend
+        p = with_defaults(params)
+        if p.planner != 'Jerk_Primitive':
+            raise NotImplementedError(f"SteppedExperimentBatch runs planner 'Jerk_Primitive' (got {p.planner!r}); ExperimentBatch runs "
+                                      'Primitive and NoMove inside the persistent closed loop')
+        if p.gaze_method not in STEPPED_GAZE_METHODS:
+            raise NotImplementedError(f'SteppedExperimentBatch: gaze_method {p.gaze_method!r}: ' + ' / '.join(STEPPED_GAZE_METHODS) +
+                                      ' (use Experiment, one episode at a time, for other host plugin classes)')
+        if not getattr(backend if backend is not None else HipBackend, 'supports_step_gaze', False):
+            raise NotImplementedError("SteppedExperimentBatch needs a backend with the step path's gaze launch (include/d2d_gaze.h)")
+        if p.gaze_method == 'NoControl':
+            p.drone_view_range = 360                                   # experiment.py:28-29
+        self.params = p
+        worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
+        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner='Jerk_Primitive', worlds=worlds,
+                                 device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie)
+        self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
+        self.steps_run = 0
+
+    def run(self, check_every=16):
+        self.steps_run = self.env.run_episodes(self.max_steps, check_every)
+        self.env.sync()
+        return self.rows()

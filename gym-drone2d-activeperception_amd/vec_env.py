@@ -18,7 +18,10 @@ Planner modes
               (include/d2d_jerk.h, one launch of libd2d_jerk.so that writes plan_ok / wp_valid / wp; the planner mode stays
               'external').  `step`, `perceive` / `act`, `rollout` and `reset` run it; `closed_loop` does not (the persistent
               kernel cannot take a stage from another library).  gaze: 'external' / None (the caller's actions), 'Rotating',
-              'NoControl'
+              'NoControl'; on a backend with the step path's gaze launch (include/d2d_gaze.h, libd2d_gaze.so) also 'LookAhead' and
+              'Owl' (yaw_planner.py:28-39, :151-222: one launch in front of the step) and 'LookGoal' and 'Oxford' (constants 0:
+              this planner's trajectory is empty at every policy call).  `policy_step()` is one step of the reference's episode
+              loop with the policy on the device; `run_episodes()` plays every env's episode to its end
 
 Motion profiles (`params.motion_profile`)
   'CVM'       the agents move with their preferred velocity, inside the fused step (D2D_ST_AGENTS)
@@ -297,12 +300,22 @@ class VecDrone2DEnv:
         self.reward = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)   # drone_v2.py:257
         self.plugins = None
         self.jerk = None
+        self.gaze_state = None             # gaze_plugin.GazeState: LookAhead / Owl as a launch in front of the step
+        self.step_gaze = None              # the gaze policy the step path evaluates itself (policy_step, run_episodes), or None
         if device_plugins and planner == 'Jerk_Primitive':
             # its own library and its own per-batch state (jerk_plugin.JerkState): no d2d_plan is involved
-            if gaze not in ('external', None, 'Rotating', 'NoControl'):
+            # LookAhead / Owl: a launch of libd2d_gaze.so in front of the step (include/d2d_gaze.h), on a backend that has it.
+            # LookGoal / Oxford: this planner's trajectory is empty at every policy call (plan() appends one waypoint, step_pos pops
+            # it), and both policies answer 0 for an empty trajectory (yaw_planner.py:235-236, :117-118): resident constants
+            step_gaze = bool(getattr(backend, 'supports_step_gaze', False))
+            if gaze not in ('external', None, 'Rotating', 'NoControl') and not step_gaze:
                 raise NotImplementedError(f"device plugins: planner 'Jerk_Primitive' / gaze {gaze!r}: the device Jerk_Primitive planner "
                                           "takes gaze 'external' (the caller's actions), 'Rotating' or 'NoControl'; drive any other "
                                           'policy from the host (gaze.LookAhead, ...) and pass its actions to step()')
+            if gaze not in ('external', None, 'Rotating', 'NoControl', 'LookAhead', 'Owl', 'LookGoal', 'Oxford'):
+                raise NotImplementedError(f"device plugins: planner 'Jerk_Primitive' / gaze {gaze!r}: the device Jerk_Primitive planner "
+                                          "takes gaze 'external' (the caller's actions), 'Rotating', 'NoControl', 'LookAhead', 'Owl', "
+                                          "'LookGoal' or 'Oxford'; drive any other policy from the host and pass its actions to step()")
             backend_for(backend, device, 'supports_jerk', "has no Jerk_Primitive planner (planner='Jerk_Primitive' with "
                         'device_plugins=True runs on the HIP backend)')
             if not kf_enabled and N:
@@ -311,8 +324,13 @@ class VecDrone2DEnv:
             self.jerk = JerkState(self.params, self.cfg, self.device, self.tracker_radius.numpy() if N and self.num_envs else None,
                                   tie=jerk_tie)
             self._jerk_call = self.jerk.call(self.state)
-            if gaze in ('Rotating', 'NoControl'):
+            if gaze in ('Rotating', 'NoControl', 'LookGoal', 'Oxford'):
                 self.state.action.fill_(1.0 if gaze == 'Rotating' else 0.0)
+            elif gaze in ('LookAhead', 'Owl'):
+                from .gaze_plugin import GazeState
+                self.gaze_state = GazeState(self.params, self.cfg, self.device, gaze)
+                self._gaze_call = self.gaze_state.call(self.state)
+            self.step_gaze = gaze if gaze not in ('external', None) else None
         elif device_plugins:
             from .device_plugins import PluginState
             gaze = gaze if gaze is not None else self.params.gaze_method
@@ -381,6 +399,60 @@ class VecDrone2DEnv:
             self.backend.run_stages(self.cfg, self._st, A.ST_ALL & ~A.ST_AGENTS)
         else:
             self.backend.step(self.cfg, self._st)
+
+    def run_gaze(self):
+        """d2d_gaze_act for every env that is not done: the action of the coming step, from what the previous step left.  The
+        constant policies (Rotating, NoControl; LookGoal and Oxford under Jerk_Primitive) keep their resident action"""
+        if self.gaze_state is not None and self.num_envs:
+            self.backend.gaze_act(self._gaze_call)
+
+    def _needs_step_gaze(self, what):
+        if self.jerk is None or self.step_gaze is None:
+            raise RuntimeError(f"{what} needs planner='Jerk_Primitive', device_plugins=True and a gaze policy the step path "
+                               "evaluates: 'LookAhead', 'Owl', 'LookGoal', 'Oxford', 'Rotating' or 'NoControl'")
+
+    def policy_step(self):
+        """One step of the reference's episode loop (experiment.py:69-70): a = policy.plan(info), then env.step(a), with the policy
+        on the device.  Returns what step() returns.  Oxford's own maps (the time since a cell was observed) are not kept: under
+        this planner they never reach an action, and nothing here makes them observable."""
+        self._needs_step_gaze('policy_step()')
+        self.run_gaze()
+        self.run_step()
+        return self._result()
+
+    def run_episodes(self, max_steps=None, check_every=16):
+        """Every env plays its episode to the end (experiment.py:66-70) and stays as it ended.  A step is d2d_gaze_act, the RVO
+        launches under RVO, d2d_run_stages(PERCEIVE | SKIP_DONE), d2d_jerk_plan, d2d_run_stages(ACT | SKIP_DONE).  Stops when every
+        env is done or after `max_steps` (default ceil(max_flight_time / dt) + 1: freezing ends every episode by then); the host
+        looks at the flags once per `check_every` steps and synchronises at no other time.  Returns the steps run.
+
+        Frozen means: drone, counters, flags, dmap, gt, kf, active, the action and the Owl state of a finished env no longer
+        change, and that is all a CSV row reads.  d2d_jerk_plan has no mask, so a finished env's plan_ok, wp, jerk_choice, jerk_stat
+        and tracker bookkeeping keep being rewritten; under RVO its agents keep moving."""
+        self._needs_step_gaze('run_episodes()')
+        n = int(np.ceil(self.params.max_flight_time / self.params.dt)) + 1 if max_steps is None else int(max_steps)
+        every = max(1, int(check_every))
+        noise = self.state.noise if self.cfg.noise_rows > 1 else None
+        perceive = A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE
+        t = 0
+        try:
+            while t < n and self.num_envs:
+                self.run_gaze()
+                if noise is not None:                 # as rollout(): a single d2d_run_stages reads the block's first row
+                    self._st.noise = noise[self.cfg.noise_row0].data_ptr()
+                if self.rvo:
+                    self._rvo_agents()
+                self.backend.run_stages(self.cfg, self._st, perceive | A.ST_SKIP_DONE)
+                self.run_jerk_plan()
+                self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
+                self._advance_noise(1)
+                t += 1
+                if t % every == 0 and t < n and bool(self.state.flags[:, A.F_DONE].all()):
+                    break
+        finally:
+            if noise is not None:
+                self._st.noise = noise.data_ptr()
+        return t
 
     def run_jerk_plan(self):
         """d2d_jerk_plan for every env: plan_ok / wp_valid / wp of this step, from what d2d_perceive left"""
@@ -553,7 +625,8 @@ class VecDrone2DEnv:
         if self.jerk is not None:
             raise NotImplementedError("closed_loop(): planner 'Jerk_Primitive' does not run inside the persistent closed loop (its "
                                       'stage lives in libd2d_jerk.so); step the env with step() / perceive() + act(), or run '
-                                      'episodes through runner.Experiment')
+                                      'episodes through runner.Experiment.  run_episodes() / runner.SteppedExperimentBatch play '
+                                      'whole episodes of this planner as a batch')
         if self.plugins is None:
             raise RuntimeError('closed_loop() needs device_plugins=True')
         if self.rvo:
@@ -575,6 +648,10 @@ class VecDrone2DEnv:
             if mask is not None:
                 mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
             self.backend.jerk_reset(self.jerk.t['trk_radius'], self.jerk.t['trk_prev'], self.jerk.trk_radius0, mask, 1)
+        if self.gaze_state is not None and self.gaze_state.owl_state is not None and self.num_envs:
+            if mask is not None:
+                mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            self.backend.gaze_reset(self.gaze_state.owl_state, mask, 1)
 
     def sync(self):
         self.backend.sync()
