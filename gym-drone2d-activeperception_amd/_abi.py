@@ -91,6 +91,8 @@ def bind(lib, prefix='d2d_'):
         'log_array': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         'rng_draw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
         'launch_shape': (C.c_int, [P(Cfg), P(Plan), P(C.c_int32 * 4)]),
+        'gaze_stage_live': (C.c_int, [P(Cfg), P(State), P(Plan), C.c_void_p]),
+        'plan_stage_live': (C.c_int, [P(Cfg), P(State), P(Plan), C.c_void_p]),
     }
     return _bind(lib, prefix, sig, OPTIONAL)
 
@@ -110,8 +112,11 @@ def _bind(lib, prefix, sig, optional=()):
 
 # atan2_array, pow2_array, log_array, rng_draw: test hooks of the HIP library alone (include/d2d_hooks.h), outside the surface the
 # oracle mirrors
-OPTIONAL = ('launch_shape', 'atan2_array', 'pow2_array', 'log_array', 'rng_draw')
+# gaze_stage_live, plan_stage_live: include/d2d_stepped.h, the stages of the HIP library for the step path's episode loop (additions:
+# an older build of the library, or the oracle, has none, and HipBackend.supports_stepped_plugins asks for them by name)
+OPTIONAL = ('launch_shape', 'atan2_array', 'pow2_array', 'log_array', 'rng_draw', 'gaze_stage_live', 'plan_stage_live')
 HIP_ONLY_ENTRY_POINTS = ('atan2_array', 'pow2_array', 'log_array', 'rng_draw')
+STEPPED_ENTRY_POINTS = ('gaze_stage_live', 'plan_stage_live')
 ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_stages', 'rollout', 'reset',
                 'tan_array', 'gaze_stage', 'plan_stage', 'closed_loop', 'plan_reset', 'sincos_array', 'launch_shape')
 
@@ -183,6 +188,21 @@ def bind_rvo(lib):
         'agents_step': (C.c_int, [V, V, D, D, D, D, I, I, V]),
     }
     return _bind(lib, 'd2d_rvo_', dict(own, **sig))
+
+
+RVO_LIVE_F_DONE = F_DONE       # include/d2d_rvo_live.h D2D_RVO_LIVE_F_DONE
+RVO_LIVE_ENTRY_POINTS = ('velocity_live', 'agents_step_live')
+
+
+def bind_rvo_live(lib):
+    """argtypes / restypes of include/d2d_rvo_live.h on the loaded libd2d_rvo.so: additions to that library, looked up as optional
+    symbols (a build without them binds nothing here, and its version is the same)."""
+    V, I, D = C.c_void_p, C.c_int32, C.c_double
+    sig = {
+        'velocity_live': (C.c_int, [V, V, V, V, I, I, I, V, V]),
+        'agents_step_live': (C.c_int, [V, V, V, D, D, D, D, I, I, V]),
+    }
+    return _bind(lib, 'd2d_rvo_', sig, RVO_LIVE_ENTRY_POINTS)
 
 
 # ---- include/d2d_jerk.h: the Jerk_Primitive planner on the device (csrc/jerk/libd2d_jerk.so, its own version) ----

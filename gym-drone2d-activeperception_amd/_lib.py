@@ -113,6 +113,8 @@ class HipBackend:
     supports_rvo = True                   # include/d2d_rvo.h: the RVO motion profile (VecDrone2DEnv with motion_profile='RVO')
     supports_jerk = True                  # include/d2d_jerk.h: the Jerk_Primitive planner (VecDrone2DEnv with planner='Jerk_Primitive')
     supports_step_gaze = True             # include/d2d_gaze.h: LookAhead / Owl as a launch in front of the step (policy_step, run_episodes)
+    supports_stepped_plugins = True       # include/d2d_stepped.h: the gaze and plan stages that leave finished envs alone (run_episodes)
+    supports_rvo_live = True              # include/d2d_rvo_live.h: the RVO launches that leave finished envs alone (run_episodes)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -160,6 +162,19 @@ class HipBackend:
 
     def plan_stage(self, cfg, st, plan):
         self._chk(self.fn['plan_stage'](C.byref(cfg), C.byref(st), C.byref(plan), self._stream()))
+
+    def _stepped(self, name):
+        if name not in self.fn:
+            raise D2DError(f'{LIB_PATH} has no d2d_{name} (include/d2d_stepped.h): rebuild it with csrc/build.sh')
+        return self.fn[name]
+
+    def gaze_stage_live(self, cfg, st, plan):
+        """d2d_gaze_stage_live: d2d_gaze_stage for the envs that are not done"""
+        self._chk(self._stepped('gaze_stage_live')(C.byref(cfg), C.byref(st), C.byref(plan), self._stream()))
+
+    def plan_stage_live(self, cfg, st, plan):
+        """d2d_plan_stage_live: d2d_plan_stage for the envs that are not done"""
+        self._chk(self._stepped('plan_stage_live')(C.byref(cfg), C.byref(st), C.byref(plan), self._stream()))
 
     def closed_loop(self, cfg, st, plan, nsteps, on_done=0, init=None):
         self._chk(self.fn['closed_loop'](C.byref(cfg), C.byref(st), C.byref(plan), nsteps, int(on_done),
@@ -237,6 +252,9 @@ class HipBackend:
     def _rvo(self, name, *args):
         if self.rfn is None:
             self.rlib, self.rfn = load_rvo_library()
+            self.rfn = dict(self.rfn, **A.bind_rvo_live(self.rlib))       # include/d2d_rvo_live.h, where the build has it
+        if name not in self.rfn:
+            raise D2DError(f'{RVO_LIB_PATH} has no d2d_rvo_{name} (include/d2d_rvo_live.h): rebuild it with csrc/rvo/build.sh')
         _check(self.rfn[name](*args, self._stream()), self.rfn, 'd2d_rvo')
 
     def rvo_velocity(self, agents, vel, pillars, vel_out):
@@ -249,6 +267,19 @@ class HipBackend:
         """d2d_rvo_agents_step: Agent.step of agents [B, 6, N] in place, moving with vel [B, 2, N]"""
         B, _, N = agents.shape
         self._rvo('agents_step', agents.data_ptr(), vel.data_ptr(), float(W_px), float(H_px), float(scale), float(dt), B, N)
+
+    def rvo_velocity_live(self, agents, vel, pillars, flags, vel_out):
+        """d2d_rvo_velocity_live: rvo_velocity for the envs whose flags [B, 4] uint8 do not say done; a finished env's vel_out is its vel"""
+        B, _, N = agents.shape
+        P = pillars.shape[1]
+        self._rvo('velocity_live', agents.data_ptr(), vel.data_ptr(), pillars.data_ptr() if P else None,
+                  None if flags is None else flags.data_ptr(), B, N, P, vel_out.data_ptr())
+
+    def rvo_agents_step_live(self, agents, vel, flags, W_px, H_px, scale, dt):
+        """d2d_rvo_agents_step_live: rvo_agents_step for the envs whose flags do not say done; a finished env's agents stay"""
+        B, _, N = agents.shape
+        self._rvo('agents_step_live', agents.data_ptr(), vel.data_ptr(), None if flags is None else flags.data_ptr(), float(W_px),
+                  float(H_px), float(scale), float(dt), B, N)
 
     def _jerk(self, name, *args):
         if self.jfn is None:

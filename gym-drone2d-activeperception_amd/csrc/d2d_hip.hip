@@ -46,6 +46,7 @@
 #endif
 #include "../../include/d2d.h"
 #include "../../include/d2d_hooks.h"
+#include "../../include/d2d_stepped.h"
 
 #define D2D_TAN_QUAL __device__ __forceinline__
 #define D2D_TAN_TBL_QUAL __device__ const
@@ -2912,6 +2913,19 @@ int d2d_plan_stage(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, void
   int rc = plan_check(c, s, p);
   if (rc) return rc;
   return plan_launch(c, s, p, false, stream);
+}
+
+// include/d2d_stepped.h: the two stages with finished envs left alone, for an episode loop the host drives step by step
+int d2d_gaze_stage_live(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, void *stream) {
+  int rc = plan_check(c, s, p);
+  if (rc) return rc;
+  return gaze_launch(c, s, p, nullptr, true, stream);
+}
+
+int d2d_plan_stage_live(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, void *stream) {
+  int rc = plan_check(c, s, p);
+  if (rc) return rc;
+  return plan_launch(c, s, p, true, stream);
 }
 
 int d2d_plan_reset(const d2d_cfg *c, const d2d_plan *p, const uint8_t *mask, int32_t mask_stride, void *stream) {

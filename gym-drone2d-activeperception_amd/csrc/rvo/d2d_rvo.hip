@@ -16,6 +16,9 @@
 //                              when that is a NaN and no key is negative.  (No finite input produces a NaN key: include/d2d_rvo.h.)
 //                  The winner's two doubles are recomputed from its index and written by lane 0.
 //   rvo_agents_step  thread = (env, agent): Agent.step, coalesced over the agents' planes.
+//   *_live         the same two for a batch with finished envs (include/d2d_rvo_live.h): the bodies are shared, the test of the env's
+//                  done flag comes first.  It is uniform over a rvo_velocity wave, which then copies the agent's velocity (lanes 0 and
+//                  1, one entry each) and ends before any cone is built.
 //
 // Arithmetic is fp64 in the reference's own operation order (d2d_rvo.h), compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -34,6 +37,7 @@
 #define D2D_ASIN_QUAL __device__ __forceinline__
 #define D2D_ASIN_TBL_QUAL __device__ const
 #include "d2d_rvo.h"
+#include "../../../include/d2d_rvo_live.h"
 
 #define WAVE 64
 #define EW_BLOCK 256
@@ -59,84 +63,24 @@ __attribute__((format(printf, 2, 3))) int failf(int rc, const char *fmt, ...) {
 __global__ __launch_bounds__(WAVE) void rvo_velocity_kernel(const double *__restrict__ agents, const double *__restrict__ vel,
                                                            const int32_t *__restrict__ pillars, int N, int P,
                                                            double *__restrict__ vel_out) {
-  extern __shared__ __attribute__((aligned(16))) double cones[];   // [6][nc]
-  const int lane = threadIdx.x;
-  const int i = (int)(blockIdx.x % (unsigned)N);
-  const size_t b = blockIdx.x / (unsigned)N;
-  const int nc = N - 1 + P;
-  const double *ag = agents + b * D2D_AF * N, *v = vel + b * 2 * N;
-  const int32_t *pil = pillars + b * P * 3;                          // (not read when P == 0)
-  const double rob_rad = ag[D2D_A_R * N] + 0.01;
-  const double pax = ag[D2D_A_PX * N + i], pay = ag[D2D_A_PY * N + i];
-  const double prefx = ag[D2D_A_VX * N + i], prefy = ag[D2D_A_VY * N + i];
-
-  for (int k = lane; k < nc; k += WAVE) d2d_rvo_cone_of(ag, v, pil, N, i, k, rob_rad, cones + k, (size_t)nc);
-  __syncthreads();
-  const double *apx = cones, *apy = cones + nc, *right = cones + 2 * nc, *left = cones + 3 * nc, *dist = cones + 4 * nc,
-               *rad = cones + 5 * nc;
-
-  double delta;
-  const int nrad = d2d_rvo_radii(d2d_vo_norm(prefx, prefy), &delta);
-  const int C = D2D_RVO_NTHETA * nrad + 1;
-
-  double best_key = INFINITY;
-  int best = NO_INDEX;
-  for (int c0 = 0; c0 < C; c0 += WAVE) {            // min(suitable_V, key=norm(v - pref))
-    const int c = c0 + lane;
-    double cx, cy, td, dx, dy;
-    d2d_rvo_candidate(c < C ? c : C - 1, nrad, delta, prefx, prefy, &cx, &cy);
-    bool suit = c < C;
-    for (int k = 0; k < nc; ++k) {
-      if (__ballot(suit) == 0ull) break;
-      if (suit && d2d_rvo_inside(cx, cy, pax, pay, apx[k], apy[k], right[k], left[k], &td, &dx, &dy)) suit = false;
-    }
-    if (suit) {
-      const double key = d2d_vo_norm(cx - prefx, cy - prefy);
-      if (key < best_key) best_key = key, best = c;  // (never a NaN, never +inf: the first candidate of the lane always enters)
-    }
-  }
-  if (__ballot(best != NO_INDEX) == 0ull) {          // min(unsuitable_V, key=0.2 / tc_V + norm(v - pref)): every candidate
-    for (int c0 = 0; c0 < C; c0 += WAVE) {
-      const int c = c0 + lane;
-      if (c >= C) continue;
-      double cx, cy, td, dx, dy, tc = 0.0;
-      bool have = false;
-      d2d_rvo_candidate(c, nrad, delta, prefx, prefy, &cx, &cy);
-      for (int k = 0; k < nc; ++k)
-        if (d2d_rvo_inside(cx, cy, pax, pay, apx[k], apy[k], right[k], left[k], &td, &dx, &dy)) {
-          const double t = d2d_rvo_tc(td, dx, dy, right[k], left[k], dist[k], rad[k]);
-          if (!have || t < tc) tc = t;
-          have = true;
-        }
-      double key = d2d_rvo_key(tc, cx, cy, prefx, prefy);
-      if (key != key) {
-        if (c != 0) continue;                        // a NaN that is not the list's first element never wins
-        key = -INFINITY;                             // the first element does, whatever follows (every other key is >= 0)
-      }
-      if (key < best_key || (key == best_key && c < best)) best_key = key, best = c;
-    }
-  }
-#pragma unroll
-  for (int m = WAVE / 2; m > 0; m >>= 1) {
-    const double ok = __shfl_xor(best_key, m, WAVE);
-    const int oi = __shfl_xor(best, m, WAVE);
-    if (ok < best_key || (ok == best_key && oi < best)) best_key = ok, best = oi;
-  }
-  if (lane == 0) {
-    double cx, cy;
-    d2d_rvo_candidate(best, nrad, delta, prefx, prefy, &cx, &cy);
-    double *out = vel_out + b * 2 * N;
-    out[i] = cx;
-    out[N + i] = cy;
-  }
+#include "d2d_rvo_wave.inc"   // the body, shared as text with rvo_velocity_live_kernel: this kernel compiles to what it always did
 }
 
-__global__ __launch_bounds__(EW_BLOCK) void rvo_agents_step_kernel(double *__restrict__ agents, const double *__restrict__ vel, double W_px,
-                                                                  double H_px, double scale, double dt, int N, long long total) {
-  const long long t = (long long)blockIdx.x * EW_BLOCK + threadIdx.x;
-  if (t >= total) return;
-  const int i = (int)(t % N);
-  const size_t b = (size_t)(t / N);
+__global__ __launch_bounds__(WAVE) void rvo_velocity_live_kernel(const double *__restrict__ agents, const double *__restrict__ vel,
+                                                                const int32_t *__restrict__ pillars,
+                                                                const uint8_t *__restrict__ flags, int N, int P,
+                                                                double *__restrict__ vel_out) {
+  const size_t env = blockIdx.x / (unsigned)N;
+  if (flags[env * 4 + D2D_RVO_LIVE_F_DONE]) {          // one env per wave: no lane goes on
+    const size_t at = env * 2 * N + (size_t)threadIdx.x * N + blockIdx.x % (unsigned)N;
+    if (threadIdx.x < 2) vel_out[at] = vel[at];
+    return;
+  }
+#include "d2d_rvo_wave.inc"
+}
+
+__device__ __forceinline__ void rvo_agent_step_of(double *agents, const double *vel, double W_px, double H_px, double scale, double dt, int N,
+                                                  size_t b, int i) {
   double *ag = agents + b * D2D_AF * N;
   const double *v = vel + b * 2 * N;
   double px = ag[D2D_A_PX * N + i], py = ag[D2D_A_PY * N + i], fx = ag[D2D_A_VX * N + i], fy = ag[D2D_A_VY * N + i];
@@ -145,6 +89,23 @@ __global__ __launch_bounds__(EW_BLOCK) void rvo_agents_step_kernel(double *__res
   ag[D2D_A_PY * N + i] = py;
   ag[D2D_A_VX * N + i] = fx;
   ag[D2D_A_VY * N + i] = fy;
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void rvo_agents_step_kernel(double *__restrict__ agents, const double *__restrict__ vel, double W_px,
+                                                                  double H_px, double scale, double dt, int N, long long total) {
+  const long long t = (long long)blockIdx.x * EW_BLOCK + threadIdx.x;
+  if (t >= total) return;
+  rvo_agent_step_of(agents, vel, W_px, H_px, scale, dt, N, (size_t)(t / N), (int)(t % N));
+}
+
+__global__ __launch_bounds__(EW_BLOCK) void rvo_agents_step_live_kernel(double *__restrict__ agents, const double *__restrict__ vel,
+                                                                       const uint8_t *__restrict__ flags, double W_px, double H_px,
+                                                                       double scale, double dt, int N, long long total) {
+  const long long t = (long long)blockIdx.x * EW_BLOCK + threadIdx.x;
+  if (t >= total) return;
+  const size_t b = (size_t)(t / N);
+  if (flags[b * 4 + D2D_RVO_LIVE_F_DONE]) return;
+  rvo_agent_step_of(agents, vel, W_px, H_px, scale, dt, N, b, (int)(t % N));
 }
 
 int check_sizes(const char *who, long long B, long long N, long long P) {
@@ -189,6 +150,31 @@ int d2d_rvo_agents_step(double *agents, const double *vel, double W_px, double H
   hipLaunchKernelGGL(rvo_agents_step_kernel, dim3((unsigned)((total + EW_BLOCK - 1) / EW_BLOCK)), dim3(EW_BLOCK), 0, (hipStream_t)stream,
                      agents, vel, W_px, H_px, scale, dt, (int)N, total);
   return launched("d2d_rvo_agents_step");
+}
+
+int d2d_rvo_velocity_live(const double *agents, const double *vel, const int32_t *pillars, const uint8_t *flags, int32_t B, int32_t N,
+                          int32_t P, double *vel_out, void *stream) {
+  if (const int rc = check_sizes("d2d_rvo_velocity_live", B, N, P)) return rc;
+  if (!flags) return fail(-1, "d2d_rvo_velocity_live: flags is NULL (d2d_rvo_velocity is the launch without a mask)");
+  if (N == 0) return 0;
+  if (!agents || !vel || !vel_out || (P > 0 && !pillars)) return fail(-1, "d2d_rvo_velocity_live: a pointer is NULL");
+  if (vel_out == vel) return fail(-1, "d2d_rvo_velocity_live: vel_out must not be vel");
+  const size_t lds = sizeof(double) * D2D_RVO_CONE_F * (size_t)(N - 1 + P);
+  hipLaunchKernelGGL(rvo_velocity_live_kernel, dim3((unsigned)((long long)B * N)), dim3(WAVE), lds, (hipStream_t)stream, agents, vel,
+                     pillars, flags, (int)N, (int)P, vel_out);
+  return launched("d2d_rvo_velocity_live");
+}
+
+int d2d_rvo_agents_step_live(double *agents, const double *vel, const uint8_t *flags, double W_px, double H_px, double scale, double dt,
+                             int32_t B, int32_t N, void *stream) {
+  if (const int rc = check_sizes("d2d_rvo_agents_step_live", B, N, 0)) return rc;
+  if (!flags) return fail(-1, "d2d_rvo_agents_step_live: flags is NULL (d2d_rvo_agents_step is the launch without a mask)");
+  if (N == 0) return 0;
+  if (!agents || !vel) return fail(-1, "d2d_rvo_agents_step_live: a pointer is NULL");
+  const long long total = (long long)B * N;
+  hipLaunchKernelGGL(rvo_agents_step_live_kernel, dim3((unsigned)((total + EW_BLOCK - 1) / EW_BLOCK)), dim3(EW_BLOCK), 0,
+                     (hipStream_t)stream, agents, vel, flags, W_px, H_px, scale, dt, (int)N, total);
+  return launched("d2d_rvo_agents_step_live");
 }
 
 }  // extern "C"

@@ -128,7 +128,8 @@ class ExperimentBatch(_BatchRows):
                                       'other host plugin classes)')
         if p.motion_profile == 'RVO':
             raise NotImplementedError("ExperimentBatch: motion_profile 'RVO' does not run inside the persistent closed loop (its stage "
-                                      'lives in libd2d_rvo.so); run the episodes through Experiment, one at a time')
+                                      'lives in libd2d_rvo.so); SteppedExperimentBatch plays the episodes of planner Primitive '
+                                      'under it as a batch (Experiment, one episode at a time, runs everything else)')
         device_heading = device_gaze and getattr(backend if backend is not None else HipBackend, 'supports_device_heading_gaze', False)
         if p.gaze_method == 'LookGoal' and not device_heading:
             raise NotImplementedError('ExperimentBatch: LookGoal needs a backend with the device LookAhead / LookGoal stage')
@@ -188,25 +189,36 @@ class SteppedExperimentBatch(_BatchRows):
     looks at the flags once every `check_every` steps.  Every `--gaze_method` name runs: LookAhead and Owl as that launch, Rotating
     and NoControl as constants, and LookGoal and Oxford as the constant 0 they are under this planner (its trajectory is empty at
     every policy call; Oxford's own maps are therefore not kept).  What a finished env still rewrites (the plan's outputs and tracker
-    bookkeeping; under RVO its agents) is nothing a row reads.  `jerk_tie`: as in VecDrone2DEnv."""
+    bookkeeping; under RVO its agents) is nothing a row reads.  `jerk_tie`: as in VecDrone2DEnv.
+
+    `planner='Primitive'` under `motion_profile='RVO'` runs here too (under CVM it stays with ExperimentBatch): the plugins of
+    libd2d_hip.so as stages that leave finished envs alone (include/d2d_stepped.h) around the RVO launches that do the same
+    (include/d2d_rvo_live.h), with Oxford, LookAhead, LookGoal and Owl as the device gaze stage.  There a finished env is frozen in
+    everything, its agents, their velocities and its plugin state included."""
 
     def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_worlds=False, jerk_tie=None):
         from .vec_env import VecDrone2DEnv, build_worlds
         from ._lib import HipBackend
         p = with_defaults(params)
-        if p.planner != 'Jerk_Primitive':
-            raise NotImplementedError(f"SteppedExperimentBatch runs planner 'Jerk_Primitive' (got {p.planner!r}); ExperimentBatch runs "
-                                      'Primitive and NoMove inside the persistent closed loop')
+        primitive_rvo = p.planner == 'Primitive' and p.motion_profile == 'RVO'     # each (planner, profile) cell has one batch runner
+        if p.planner != 'Jerk_Primitive' and not primitive_rvo:
+            raise NotImplementedError(f"SteppedExperimentBatch runs planner 'Jerk_Primitive' (got {p.planner!r}), and planner "
+                                      "'Primitive' under motion_profile 'RVO'; ExperimentBatch runs Primitive and NoMove inside the "
+                                      'persistent closed loop')
         if p.gaze_method not in STEPPED_GAZE_METHODS:
             raise NotImplementedError(f'SteppedExperimentBatch: gaze_method {p.gaze_method!r}: ' + ' / '.join(STEPPED_GAZE_METHODS) +
                                       ' (use Experiment, one episode at a time, for other host plugin classes)')
-        if not getattr(backend if backend is not None else HipBackend, 'supports_step_gaze', False):
+        have = lambda flag: getattr(backend if backend is not None else HipBackend, flag, False)   # noqa: E731
+        if primitive_rvo and not (have('supports_stepped_plugins') and have('supports_rvo_live')):
+            raise NotImplementedError("SteppedExperimentBatch: planner 'Primitive' under motion_profile 'RVO' needs a backend with the "
+                                      'stages and RVO launches that leave finished envs alone (include/d2d_stepped.h, d2d_rvo_live.h)')
+        if not primitive_rvo and not have('supports_step_gaze'):
             raise NotImplementedError("SteppedExperimentBatch needs a backend with the step path's gaze launch (include/d2d_gaze.h)")
         if p.gaze_method == 'NoControl':
             p.drone_view_range = 360                                   # experiment.py:28-29
         self.params = p
         worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
-        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner='Jerk_Primitive', worlds=worlds,
+        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
                                  device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie)
         self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
         self.steps_run = 0

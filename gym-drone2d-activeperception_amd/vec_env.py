@@ -13,7 +13,8 @@ Planner modes
               the step; with `gaze='Oxford'` yaw_planner.py:41-127 supplies the action on the device as well
               (`closed_loop()`: gaze -> perceive -> plan -> act, no host round trip); `gaze='LookAhead'` / `'LookGoal'`
               (yaw_planner.py:18-39 / :225-257) and `gaze='Owl'` (:151-222) run on the device the same way on a backend
-              that has them
+              that has them.  `policy_step()` / `run_episodes()` drive the same stages step by step from the host
+              (include/d2d_stepped.h), which is how the episodes of this planner run under motion_profile 'RVO'
   'Jerk_Primitive' with `device_plugins=True`: traj_planner.py:403-516 runs on the device between the two halves of the step
               (include/d2d_jerk.h, one launch of libd2d_jerk.so that writes plan_ok / wp_valid / wp; the planner mode stays
               'external').  `step`, `perceive` / `act`, `rollout` and `reset` run it; `closed_loop` does not (the persistent
@@ -28,7 +29,8 @@ Motion profiles (`params.motion_profile`)
   'RVO'       utils.py:299-460: every agent first picks a velocity outside the others' reciprocal velocity obstacles
               (include/d2d_rvo.h, two launches of libd2d_rvo.so), then the fused step runs without its agents stage.
               `step`, `perceive` / `act`, `rollout` and `reset` run it; `closed_loop` does not (the persistent kernel cannot take
-              a stage from another library)
+              a stage from another library).  `policy_step` / `run_episodes` play whole episodes under it, for the Jerk_Primitive
+              planner and, with the launches of include/d2d_rvo_live.h, for the Primitive plugins
 """
 import numpy as np
 import torch
@@ -360,6 +362,9 @@ class VecDrone2DEnv:
                 self.state.action.fill_(1.0)
             elif gaze == 'NoControl':
                 self.state.action.fill_(0.0)
+            # the step path's episode loop (policy_step, run_episodes) takes the Primitive plugins with a policy of their own
+            if planner == 'Primitive' and gaze not in ('external', None):
+                self.step_gaze = gaze
 
     # ------------------------------------------------------------------ gym-like surface (batched)
     @property
@@ -387,6 +392,16 @@ class VecDrone2DEnv:
         self.backend.rvo_agents_step(s.agents, s.agent_vel_out, self.cfg.W_px, self.cfg.H_px, self.cfg.scale, self.cfg.dt)
         s.t['agent_vel'], s.t['agent_vel_out'] = s.t['agent_vel_out'], s.t['agent_vel']
 
+    def _rvo_agents_live(self):
+        """_rvo_agents for the envs that are not done (include/d2d_rvo_live.h): a finished env's agents stay where they are, and its
+        velocities go through the swap unchanged"""
+        s = self.state
+        if self.num_envs == 0:
+            return
+        self.backend.rvo_velocity_live(s.agents, s.agent_vel, s.pillars, s.flags, s.agent_vel_out)
+        self.backend.rvo_agents_step_live(s.agents, s.agent_vel_out, s.flags, self.cfg.W_px, self.cfg.H_px, self.cfg.scale, self.cfg.dt)
+        s.t['agent_vel'], s.t['agent_vel_out'] = s.t['agent_vel_out'], s.t['agent_vel']
+
     def run_step(self):
         """d2d_step with the action already set; under RVO the agents move first, then every other stage (the state machine stage,
         which d2d_step runs before the agents, does not touch them: the order is the reference's)"""
@@ -407,15 +422,47 @@ class VecDrone2DEnv:
             self.backend.gaze_act(self._gaze_call)
 
     def _needs_step_gaze(self, what):
-        if self.jerk is None or self.step_gaze is None:
-            raise RuntimeError(f"{what} needs planner='Jerk_Primitive', device_plugins=True and a gaze policy the step path "
-                               "evaluates: 'LookAhead', 'Owl', 'LookGoal', 'Oxford', 'Rotating' or 'NoControl'")
+        if self.step_gaze is None:
+            raise RuntimeError(f"{what} needs planner='Jerk_Primitive' or 'Primitive', device_plugins=True and a gaze policy the step "
+                               "path evaluates: 'LookAhead', 'Owl', 'LookGoal', 'Oxford', 'Rotating' or 'NoControl'")
+        if self.plugins is not None:
+            backend_for(self.backend, None, 'supports_stepped_plugins', f'has no gaze and plan stages that leave finished envs alone '
+                        f'(include/d2d_stepped.h): {what} with the Primitive plugins runs on the HIP backend')
+            if self.rvo:
+                backend_for(self.backend, None, 'supports_rvo_live', f'has no RVO launches that leave finished envs alone '
+                            f'(include/d2d_rvo_live.h): {what} with the Primitive plugins under RVO runs on the HIP backend')
+
+    def _plugins_step(self):
+        """One step of the episode loop with the Primitive plugins, finished envs left alone by every launch: d2d_gaze_stage_live
+        (nothing for the resident constants), under RVO the two _live RVO launches, d2d_run_stages(PERCEIVE | SKIP_DONE) with this
+        step's row of the noise, d2d_plan_stage_live, d2d_run_stages(ACT | SKIP_DONE).  The gaze decision reads the drone, the
+        trajectory, seen_step and the trackers, none of which the RVO launches write, so the order is the reference's: policy.plan,
+        then step() with the agents first"""
+        noise = self.state.noise if self.cfg.noise_rows > 1 else None
+        try:
+            if self._plan.gaze != A.GAZE_NONE:
+                self.backend.gaze_stage_live(self.cfg, self._st, self._plan)
+            if noise is not None:                     # as rollout(): a single d2d_run_stages reads the block's first row
+                self._st.noise = noise[self.cfg.noise_row0].data_ptr()
+            if self.rvo:
+                self._rvo_agents_live()
+            self.backend.run_stages(self.cfg, self._st, (A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE) | A.ST_SKIP_DONE)
+            self.backend.plan_stage_live(self.cfg, self._st, self._plan)
+            self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
+            self._advance_noise(1)
+        finally:
+            if noise is not None:
+                self._st.noise = noise.data_ptr()
 
     def policy_step(self):
         """One step of the reference's episode loop (experiment.py:69-70): a = policy.plan(info), then env.step(a), with the policy
         on the device.  Returns what step() returns.  Oxford's own maps (the time since a cell was observed) are not kept: under
         this planner they never reach an action, and nothing here makes them observable."""
         self._needs_step_gaze('policy_step()')
+        if self.plugins is not None:       # the Primitive plugins: one step of run_episodes' loop (an env that is done stays as it is)
+            if self.num_envs:
+                self._plugins_step()
+            return self._result()
         self.run_gaze()
         self.run_step()
         return self._result()
@@ -428,10 +475,24 @@ class VecDrone2DEnv:
 
         Frozen means: drone, counters, flags, dmap, gt, kf, active, the action and the Owl state of a finished env no longer
         change, and that is all a CSV row reads.  d2d_jerk_plan has no mask, so a finished env's plan_ok, wp, jerk_choice, jerk_stat
-        and tracker bookkeeping keep being rewritten; under RVO its agents keep moving."""
+        and tracker bookkeeping keep being rewritten; under RVO its agents keep moving.
+
+        With the Primitive plugins (planner='Primitive', under either motion profile) a step is d2d_gaze_stage_live, under RVO the two
+        launches of include/d2d_rvo_live.h, d2d_run_stages(PERCEIVE | SKIP_DONE), d2d_plan_stage_live, d2d_run_stages(ACT | SKIP_DONE),
+        and a finished env is frozen in everything: the fields above, its agents and their velocities, plan_ok / wp_valid / wp and
+        its plugin state (trajectory, header, boxes, seen_step, the Owl scores and held decision, the tracker bookkeeping).  reset()
+        with a mask between two calls starts a fresh episode, policy and trajectory for the envs of the mask alone."""
         self._needs_step_gaze('run_episodes()')
         n = int(np.ceil(self.params.max_flight_time / self.params.dt)) + 1 if max_steps is None else int(max_steps)
         every = max(1, int(check_every))
+        if self.plugins is not None:
+            t = 0
+            while t < n and self.num_envs:
+                self._plugins_step()
+                t += 1
+                if t % every == 0 and t < n and bool(self.state.flags[:, A.F_DONE].all()):
+                    break
+            return t
         noise = self.state.noise if self.cfg.noise_rows > 1 else None
         perceive = A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE
         t = 0
@@ -632,7 +693,8 @@ class VecDrone2DEnv:
         if self.rvo:
             raise NotImplementedError("closed_loop(): motion_profile 'RVO' does not run inside the persistent closed loop (its stage "
                                       'lives in libd2d_rvo.so); step the env with step() / perceive() + act(), or run episodes '
-                                      'through runner.Experiment')
+                                      'through runner.Experiment.  run_episodes() / runner.SteppedExperimentBatch play whole '
+                                      'episodes under this profile as a batch')
         mode = A.DONE_RESET if auto_reset else (A.DONE_FREEZE if freeze_done else A.DONE_CONTINUE)
         self.backend.closed_loop(self.cfg, self._st, self._plan, int(nsteps), mode,
                                  self._init_st if auto_reset else None)
