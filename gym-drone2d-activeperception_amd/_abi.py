@@ -233,6 +233,17 @@ def bind_jerk(lib):
     return _bind(lib, 'd2d_jerk_', sig)
 
 
+JERK_LIVE_F_DONE = F_DONE      # include/d2d_jerk_live.h D2D_JERK_LIVE_F_DONE
+JERK_LIVE_ENTRY_POINTS = ('plan_live',)
+
+
+def bind_jerk_live(lib):
+    """argtypes / restypes of include/d2d_jerk_live.h on the loaded libd2d_jerk.so: an addition to that library, looked up as an
+    optional symbol (a build without it binds nothing here, and its version is the same)."""
+    sig = {'plan_live': (C.c_int, [C.POINTER(JerkCall), C.c_void_p, C.c_void_p])}
+    return _bind(lib, 'd2d_jerk_', sig, JERK_LIVE_ENTRY_POINTS)
+
+
 # ---- include/d2d_gaze.h: the gaze decision of the step path on the device (csrc/gaze/libd2d_gaze.so, its own version) ----
 D2D_GAZE_VERSION = 1
 GAZE_K_LOOKAHEAD, GAZE_K_OWL = GAZE_LOOKAHEAD, GAZE_OWL

@@ -281,14 +281,31 @@ class HipBackend:
         self._rvo('agents_step_live', agents.data_ptr(), vel.data_ptr(), None if flags is None else flags.data_ptr(), float(W_px),
                   float(H_px), float(scale), float(dt), B, N)
 
-    def _jerk(self, name, *args):
+    def _jerk_fn(self):
         if self.jfn is None:
             self.jlib, self.jfn = load_jerk_library()
-        _check(self.jfn[name](*args, self._stream()), self.jfn, 'd2d_jerk')
+            self.jfn = dict(self.jfn, **A.bind_jerk_live(self.jlib))      # include/d2d_jerk_live.h, where the build has it
+        return self.jfn
+
+    def _jerk(self, name, *args):
+        fn = self._jerk_fn()
+        if name not in fn:
+            raise D2DError(f'{JERK_LIB_PATH} has no d2d_jerk_{name} (include/d2d_jerk_live.h): rebuild it with csrc/jerk/build.sh')
+        _check(fn[name](*args, self._stream()), fn, 'd2d_jerk')
+
+    @property
+    def supports_jerk_live(self):
+        """include/d2d_jerk_live.h: the plan launch that leaves finished envs alone (run_episodes).  An optional symbol of
+        libd2d_jerk.so: true where the built library has it"""
+        return 'plan_live' in self._jerk_fn()
 
     def jerk_plan(self, call):
         """d2d_jerk_plan: `call` is an _abi.JerkCall of device pointers (jerk_plugin.JerkState.call)"""
         self._jerk('plan', C.byref(call))
+
+    def jerk_plan_live(self, call, flags):
+        """d2d_jerk_plan_live: jerk_plan for the envs whose flags [B, 4] uint8 do not say done; nothing of a finished env is written"""
+        self._jerk('plan_live', C.byref(call), None if flags is None else flags.data_ptr())
 
     def jerk_reset(self, trk_radius, trk_prev, trk_radius0, mask=None, mask_stride=1):
         """d2d_jerk_reset: trk_radius [B, N] float64 <- trk_radius0, trk_prev [B, N] uint8 <- 0, for the envs of mask (or all)"""

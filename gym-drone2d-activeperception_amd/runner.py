@@ -188,8 +188,10 @@ class SteppedExperimentBatch(_BatchRows):
     first half of the step, the plan (include/d2d_jerk.h), the second half; finished envs are frozen (D2D_ST_SKIP_DONE) and the host
     looks at the flags once every `check_every` steps.  Every `--gaze_method` name runs: LookAhead and Owl as that launch, Rotating
     and NoControl as constants, and LookGoal and Oxford as the constant 0 they are under this planner (its trajectory is empty at
-    every policy call; Oxford's own maps are therefore not kept).  What a finished env still rewrites (the plan's outputs and tracker
-    bookkeeping; under RVO its agents) is nothing a row reads.  `jerk_tie`: as in VecDrone2DEnv.
+    every policy call; Oxford's own maps are therefore not kept).  On a backend with the launches of include/d2d_jerk_live.h and
+    d2d_rvo_live.h (the HIP backend) every launch leaves finished envs alone and a finished env is frozen in everything; on one
+    without them the plan's outputs and tracker bookkeeping (under RVO its agents) go on changing, which is nothing a row reads
+    (VecDrone2DEnv.run_episodes, `live`).  `jerk_tie`: as in VecDrone2DEnv.
 
     `planner='Primitive'` under `motion_profile='RVO'` runs here too (under CVM it stays with ExperimentBatch): the plugins of
     libd2d_hip.so as stages that leave finished envs alone (include/d2d_stepped.h) around the RVO launches that do the same

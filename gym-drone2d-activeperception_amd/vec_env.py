@@ -30,7 +30,8 @@ Motion profiles (`params.motion_profile`)
               (include/d2d_rvo.h, two launches of libd2d_rvo.so), then the fused step runs without its agents stage.
               `step`, `perceive` / `act`, `rollout` and `reset` run it; `closed_loop` does not (the persistent kernel cannot take
               a stage from another library).  `policy_step` / `run_episodes` play whole episodes under it, for the Jerk_Primitive
-              planner and, with the launches of include/d2d_rvo_live.h, for the Primitive plugins
+              planner and for the Primitive plugins; `run_episodes` moves the agents with the launches of include/d2d_rvo_live.h,
+              which leave finished envs alone
 """
 import numpy as np
 import torch
@@ -432,6 +433,20 @@ class VecDrone2DEnv:
                 backend_for(self.backend, None, 'supports_rvo_live', f'has no RVO launches that leave finished envs alone '
                             f'(include/d2d_rvo_live.h): {what} with the Primitive plugins under RVO runs on the HIP backend')
 
+    def _jerk_live(self, live):
+        """Does run_episodes() with planner='Jerk_Primitive' take the launches that leave finished envs alone?  `live` None: where
+        the backend has them; True: they are required; False: no"""
+        if live is not None and not live:
+            return False
+        lacks = [(flag, what) for flag, what, needed in (
+            ('supports_jerk_live', 'has no plan launch that leaves finished envs alone (include/d2d_jerk_live.h)', True),
+            ('supports_rvo_live', 'has no RVO launches that leave finished envs alone (include/d2d_rvo_live.h)', self.rvo))
+            if needed and not getattr(self.backend, flag, False)]
+        if lacks and live:
+            backend_for(self.backend, None, lacks[0][0], f"{lacks[0][1]}: run_episodes(live=True) with planner 'Jerk_Primitive'"
+                        f"{' under RVO' if self.rvo else ''} runs on the HIP backend")
+        return not lacks
+
     def _plugins_step(self):
         """One step of the episode loop with the Primitive plugins, finished envs left alone by every launch: d2d_gaze_stage_live
         (nothing for the resident constants), under RVO the two _live RVO launches, d2d_run_stages(PERCEIVE | SKIP_DONE) with this
@@ -467,15 +482,27 @@ class VecDrone2DEnv:
         self.run_step()
         return self._result()
 
-    def run_episodes(self, max_steps=None, check_every=16):
-        """Every env plays its episode to the end (experiment.py:66-70) and stays as it ended.  A step is d2d_gaze_act, the RVO
-        launches under RVO, d2d_run_stages(PERCEIVE | SKIP_DONE), d2d_jerk_plan, d2d_run_stages(ACT | SKIP_DONE).  Stops when every
-        env is done or after `max_steps` (default ceil(max_flight_time / dt) + 1: freezing ends every episode by then); the host
-        looks at the flags once per `check_every` steps and synchronises at no other time.  Returns the steps run.
+    def run_episodes(self, max_steps=None, check_every=16, live=None):
+        """Every env plays its episode to the end (experiment.py:66-70) and stays as it ended.  Stops when every env is done or after
+        `max_steps` (default ceil(max_flight_time / dt) + 1: freezing ends every episode by then); the host looks at the flags once
+        per `check_every` steps and synchronises at no other time.  Returns the steps run.
 
-        Frozen means: drone, counters, flags, dmap, gt, kf, active, the action and the Owl state of a finished env no longer
-        change, and that is all a CSV row reads.  d2d_jerk_plan has no mask, so a finished env's plan_ok, wp, jerk_choice, jerk_stat
-        and tracker bookkeeping keep being rewritten; under RVO its agents keep moving.
+        With planner='Jerk_Primitive' a step is d2d_gaze_act, the two launches of include/d2d_rvo_live.h under RVO,
+        d2d_run_stages(PERCEIVE | SKIP_DONE), d2d_jerk_plan_live (include/d2d_jerk_live.h), d2d_run_stages(ACT | SKIP_DONE): every
+        launch leaves finished envs alone, and a finished env is frozen in everything -- drone, counters, flags, dmap, gt, kf,
+        active, the action, the Owl state, its agents and their velocities, plan_ok / wp_valid / wp, jerk_choice, jerk_stat and the
+        tracker bookkeeping are those of the step that ended its episode, as in a one-env run of the same world.  (Of the two
+        velocity buffers that swap every step, agent_vel is the velocity; agent_vel_out is the scratch half, into which a masked
+        launch copies a finished env's velocity so that the swap keeps it.)
+
+        `live` chooses the loop for this planner.  None: the masked launches where the backend has them (supports_jerk_live, under
+        RVO also supports_rvo_live), else the loop below.  True: the masked launches, NotImplementedError where the backend lacks
+        one.  False: d2d_jerk_plan and, under RVO, the two launches of include/d2d_rvo.h for every env, finished or not, launch for
+        launch the loop of before the masked launches existed: drone, counters, flags, dmap, gt, kf, active, the action and the Owl
+        state of a finished env are still frozen, and that is all a CSV row reads, but its plan_ok, wp, jerk_choice, jerk_stat and
+        tracker bookkeeping keep being rewritten and under RVO its agents keep moving.  It is there for A/B measurement
+        (tools/jerk_episodes_bench.py) and for a caller that depended on it.  The Primitive plugins take no `live`: their loop
+        is masked throughout.
 
         With the Primitive plugins (planner='Primitive', under either motion profile) a step is d2d_gaze_stage_live, under RVO the two
         launches of include/d2d_rvo_live.h, d2d_run_stages(PERCEIVE | SKIP_DONE), d2d_plan_stage_live, d2d_run_stages(ACT | SKIP_DONE),
@@ -493,6 +520,7 @@ class VecDrone2DEnv:
                 if t % every == 0 and t < n and bool(self.state.flags[:, A.F_DONE].all()):
                     break
             return t
+        live = self._jerk_live(live)
         noise = self.state.noise if self.cfg.noise_rows > 1 else None
         perceive = A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE
         t = 0
@@ -502,9 +530,12 @@ class VecDrone2DEnv:
                 if noise is not None:                 # as rollout(): a single d2d_run_stages reads the block's first row
                     self._st.noise = noise[self.cfg.noise_row0].data_ptr()
                 if self.rvo:
-                    self._rvo_agents()
+                    self._rvo_agents_live() if live else self._rvo_agents()
                 self.backend.run_stages(self.cfg, self._st, perceive | A.ST_SKIP_DONE)
-                self.run_jerk_plan()
+                if live:
+                    self.backend.jerk_plan_live(self._jerk_call, self.state.flags)
+                else:
+                    self.run_jerk_plan()
                 self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
                 self._advance_noise(1)
                 t += 1

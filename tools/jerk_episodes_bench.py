@@ -13,7 +13,17 @@ Shape: 4096 envs x 10 agents of the README world at drone_max_speed = 40, for ga
 Also recorded: the reference's seconds per step from tests/golden/jerk_traces.npz (one env, on the recording machine's CPU) and the
 compiler's resource report of the kernels for gfx950 (--resources-only stops after it and needs no GPU).
 
-python tools/jerk_episodes_bench.py --out profiles/jerk_episodes.json"""
+--live-ab JSON runs the other measurement and stops: run_episodes(live=True), every launch leaving finished envs alone
+(include/d2d_jerk_live.h, include/d2d_rvo_live.h), against run_episodes(live=False), the loop of before, for CVM and RVO x Owl and
+LookAhead at --envs envs.  Both forms in this one process, alternating, `--reps` times each, every run kept:
+  whole    run_episodes() to the end after an untimed reset
+  early    the first steps, one fewer than the earliest ending of that batch (taken from the whole run's own step counters): no env is
+           done, so this is what the masks cost where they save nothing
+  plan     d2d_jerk_plan_live and d2d_jerk_plan alone, --calls launches between one pair of events, on the state after the early steps
+The summary holds the medians, the ratio of the medians and the span (max - min) of the baseline's own runs.
+
+python tools/jerk_episodes_bench.py --out profiles/jerk_episodes.json
+python tools/jerk_episodes_bench.py --reps 5 --live-ab profiles/jerk_episodes_live.json"""
 import argparse
 import json
 import os
@@ -97,8 +107,74 @@ def between_events(fn, torch):
     return t0.elapsed_time(t1) * 1e-3, time.perf_counter() - w, out
 
 
+def live_ab(args):
+    """run_episodes(live=True) against run_episodes(live=False): see the module's docstring"""
+    import statistics
+    import warnings
+    import torch
+    import drone2d_amd as pkg
+    from drone2d_amd import _abi as A, _lib, runner
+    warnings.simplefilter('ignore')
+    hip = _lib.HipBackend()
+    forms = (('masked', True), ('unmasked', False))
+    result = dict(tool='tools/jerk_episodes_bench.py --live-ab', device=torch.cuda.get_device_name(0), reps=args.reps, envs=args.envs,
+                  world=WORLD, forms={k: f'run_episodes(live={v})' for k, v in forms}, runs=[], summary=[])
+
+    def emit(rec):
+        result['runs'].append(rec)
+        print(json.dumps(rec), flush=True)
+
+    def repeat(fn, n):
+        for _ in range(n):
+            fn()
+
+    for profile in ('CVM', 'RVO'):
+        for g in ('Owl', 'LookAhead'):
+            p = pkg.Params(planner='Jerk_Primitive', gaze_method=g, motion_profile=profile, **WORLD)
+            xb = runner.SteppedExperimentBatch(p, args.envs, backend=hip, device_worlds=True)
+            env = xb.env
+            for _, live in forms:                           # untimed: one whole run of either form (code objects, allocator)
+                env.reset()
+                env.run_episodes(xb.max_steps, live=live)
+            hip.sync()
+            early = max(1, int(env.state.counters[:, A.C_STEPS].min()) - 1)
+            rows = {}
+            for rep in range(args.reps):
+                for form, live in forms:
+                    env.reset()
+                    sec, wall, steps = between_events(lambda: env.run_episodes(xb.max_steps, live=live), torch)
+                    rows[form] = xb.rows()
+                    emit(dict(rep=rep, profile=profile, gaze=g, form=form, what='whole', steps=steps, seconds=sec, wall_seconds=wall,
+                              ms_per_step=1e3 * sec / steps, first_ending=int(env.state.counters[:, A.C_STEPS].min())))
+                for form, live in forms:
+                    env.reset()
+                    sec, wall, steps = between_events(lambda: env.run_episodes(early, check_every=10 ** 9, live=live), torch)
+                    emit(dict(rep=rep, profile=profile, gaze=g, form=form, what='early', steps=steps, seconds=sec, wall_seconds=wall,
+                              ms_per_step=1e3 * sec / steps, envs_done=int(env.state.flags[:, A.F_DONE].sum())))
+                for form, fn in (('masked', lambda: hip.jerk_plan_live(env._jerk_call, env.state.flags)), ('unmasked', env.run_jerk_plan)):
+                    sec, _, _ = between_events(lambda: repeat(fn, args.calls), torch)
+                    emit(dict(rep=rep, profile=profile, gaze=g, form=form, what='plan', after_steps=early, calls=args.calls,
+                              microseconds_per_call=1e6 * sec / args.calls))
+            same = sum(all((x != x and y != y) or x == y for x, y in zip(a, b)) for a, b in zip(rows['masked'], rows['unmasked']))
+            for what, key in (('whole', 'seconds'), ('early', 'ms_per_step'), ('plan', 'microseconds_per_call')):
+                v = {form: [r[key] for r in result['runs'] if (r['profile'], r['gaze'], r['what'], r['form']) == (profile, g, what, form)]
+                     for form, _ in forms}
+                med = {form: statistics.median(x) for form, x in v.items()}
+                result['summary'].append(dict(profile=profile, gaze=g, what=what, unit=key, median=med,
+                                              masked_over_unmasked=med['masked'] / med['unmasked'],
+                                              unmasked_span=max(v['unmasked']) - min(v['unmasked']),
+                                              masked_span=max(v['masked']) - min(v['masked']),
+                                              rows_equal=f'{same} of {args.envs}' if what == 'whole' else None))
+                print(json.dumps(result['summary'][-1]), flush=True)
+            del xb, env
+    os.makedirs(os.path.dirname(os.path.abspath(args.live_ab)), exist_ok=True)
+    with open(args.live_ab, 'w') as f:
+        json.dump(result, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--live-ab', metavar='JSON', help='the A/B of run_episodes(live=True) against live=False alone, written there')
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--envs', type=int, default=4096)
     ap.add_argument('--host-envs', type=int, default=256)
@@ -113,6 +189,8 @@ def main():
         with open(args.resources_only, 'w') as f:
             json.dump(resources(), f, indent=1)
         return
+    if args.live_ab:
+        return live_ab(args)
     import warnings
     import numpy as np
     import torch
