@@ -151,6 +151,28 @@ def bind_worlds(lib):
     return _bind(lib, 'd2d_worlds_', sig)
 
 
+# include/d2d_worlds_stream.h: the launches that refill the finished slots of a resident batch with the next seeded episodes
+STREAM_F_DONE = F_DONE         # D2D_STREAM_F_DONE
+STREAM_ROW_F = 8
+STREAM_R_STEPS, STREAM_R_SM, STREAM_R_BUF_N, STREAM_R_BUF_TS, STREAM_R_FLAG0, STREAM_R_DMAP = 0, 1, 2, 3, 4, 7
+STREAM_BUILD_FAILED = 0        # column STREAM_R_STEPS of an episode whose world hit max_attempts
+STREAM_MAX_EPISODES = 0x0fffffff
+STREAM_ENTRY_POINTS = ('stream_harvest', 'stream_assign', 'worlds_build_masked', 'stream_clear')
+
+
+def bind_worlds_stream(lib):
+    """argtypes / restypes of include/d2d_worlds_stream.h on the loaded libd2d_worlds.so: additions to that library, looked up as
+    optional symbols (a build without them binds nothing here, and its version is the same)."""
+    P, V, I = C.POINTER, C.c_void_p, C.c_int32
+    sig = {
+        'stream_harvest': (C.c_int, [P(State), V, I, I, I, I, C.c_int64, V, V]),
+        'stream_assign': (C.c_int, [V, I, C.c_int64, C.c_uint32, V, V, V, V, V]),
+        'worlds_build_masked': (C.c_int, [P(WorldSpec), P(State), V, V]),
+        'stream_clear': (C.c_int, [V, C.c_int64, V, I, V]),
+    }
+    return _bind(lib, 'd2d_', sig, STREAM_ENTRY_POINTS)
+
+
 # ---- include/d2d_metrics.h: the difficulty metrics on the device (csrc/metrics/libd2d_metrics.so, its own version) ----
 D2D_METRICS_VERSION = 2
 VO_MAX_B, VO_MAX_P, VO_MAX_ELEMS = 65535, 64 * 65535, 0x7fffffff

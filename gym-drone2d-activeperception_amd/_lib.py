@@ -124,6 +124,7 @@ class HipBackend:
         self.device = torch.device(device)
         self.lib, self.fn = load_library()
         self.wlib, self.wfn = load_worlds_library()
+        self.sfn = A.bind_worlds_stream(self.wlib)                        # include/d2d_worlds_stream.h, where the build has it
         self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
         self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
         self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
@@ -203,6 +204,37 @@ class HipBackend:
     def build_worlds(self, spec, st):
         """d2d_worlds_build: fill the world fields behind `st` for the envs of `spec` (vec_env.world_spec) on the current stream"""
         _check(self.wfn['build'](C.byref(spec), C.byref(st), self._stream()), self.wfn, 'd2d_worlds')
+
+    @property
+    def supports_episode_stream(self):
+        """include/d2d_worlds_stream.h: the launches that refill finished slots with the next seeded episodes (stream_episodes).
+        Optional symbols of libd2d_worlds.so: true where the built library has all of them"""
+        return all(n in self.sfn for n in A.STREAM_ENTRY_POINTS)
+
+    def _stream_fn(self, name, *args):
+        if name not in self.sfn:
+            raise D2DError(f'{WORLDS_LIB_PATH} has no d2d_{name} (include/d2d_worlds_stream.h): rebuild it with csrc/worlds/build.sh')
+        _check(self.sfn[name](*args, self._stream()), self.wfn, 'd2d_worlds')
+
+    def stream_harvest(self, cfg, st, slot_episode, rows):
+        """d2d_stream_harvest: every slot that is done and not retired writes its record to rows [M, 8] int32 at slot_episode[e]"""
+        self._stream_fn('stream_harvest', C.byref(st), slot_episode.data_ptr(), slot_episode.shape[0], cfg.W, cfg.H, cfg.grid_tile,
+                        rows.shape[0], rows.data_ptr())
+
+    def stream_assign(self, flags, num_episodes, map_id0, slot_episode, map_id, refill, counts):
+        """d2d_stream_assign: the slots just harvested get the next episodes in slot order (slot_episode, map_id, refill byte), or
+        retire; counts [2] int64 = (cursor, finished) moves on"""
+        self._stream_fn('stream_assign', flags.data_ptr(), slot_episode.shape[0], int(num_episodes), int(map_id0), slot_episode.data_ptr(),
+                        map_id.data_ptr(), refill.data_ptr(), counts.data_ptr())
+
+    def build_worlds_masked(self, spec, st, refill):
+        """d2d_worlds_build_masked: build_worlds for the slots with refill [B] uint8 set, nothing of any other slot"""
+        self._stream_fn('worlds_build_masked', C.byref(spec), C.byref(st), refill.data_ptr())
+
+    def stream_clear(self, t, refill):
+        """d2d_stream_clear: rows e of the per-slot tensor t [B, ...] with refill [B] uint8 set become 0, nothing else is written"""
+        if t.numel():
+            self._stream_fn('stream_clear', t.data_ptr(), t[0].numel() * t.element_size(), refill.data_ptr(), t.shape[0])
 
     def _metrics(self, name, *args):
         if self.mfn is None:

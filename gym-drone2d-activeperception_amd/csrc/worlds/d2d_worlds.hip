@@ -19,6 +19,10 @@
 //   grids       lane = four consecutive bytes of the env's grid storage, row-major or tiled; the agents' DYNAMIC cells follow
 //               behind a workgroup barrier, and since they all write the same value their order does not matter.
 //
+// The episode stream (include/d2d_worlds_stream.h) lives here too: worlds_build_masked_kernel is the same body (d2d_worlds_build.inc,
+// shared as text) behind a refill byte, stream_harvest_kernel (one wave per slot) records a finished slot's row, stream_assign_kernel
+// (one workgroup) hands the finished slots their next map ids by a ballot scan, stream_clear_kernel zeroes a refilled slot's rows of a buffer.
+//
 // Every loop is bounded by d2d_world_spec.max_attempts or by a size of the spec.  Arithmetic is fp64 in the reference's own
 // operation order, compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -35,6 +39,7 @@
 #define D2D_POW2_QUAL __device__ __forceinline__
 #define D2D_POW2_TBL_QUAL __device__ const
 #include "d2d_worlds.h"
+#include "../../../include/d2d_worlds_stream.h"
 
 #define WAVE 64
 
@@ -101,178 +106,129 @@ __device__ __forceinline__ double shfl_f64(double v, int src) {
 }
 
 __global__ __launch_bounds__(WAVE) void worlds_build_kernel(const d2d_world_spec s, const d2d_state st) {
-  extern __shared__ double lds[];
-  const int e = blockIdx.x, lane = threadIdx.x;
-  const int N = s.N, nr = s.n_rand, P = s.P, T = s.T, W = s.W, H = s.H, tile = s.grid_tile, cap = s.max_attempts;
-  double *acc = lds;                                  // [nr][D2D_W_ACC_F]
-  uint32_t *buf = (uint32_t *)(acc + (size_t)D2D_W_ACC_F * nr);   // [D2D_W_BUF]
-  int32_t *pil = (int32_t *)(buf + D2D_W_BUF);        // [P][3]
-  uint32_t *key = buf + D2D_W_CARRY;
-  const double *par = s.env_par + (size_t)e * D2D_WORLDS_ENV_F, *tgt = s.env_tgt + (size_t)e * T * 2;
-  const uint32_t seed = s.map_id[e];
-  const double scale = (double)s.scale;
+#include "d2d_worlds_build.inc"   // the body, shared as text with worlds_build_masked_kernel: this kernel compiles to what it always did
+}
 
-  // ---- the Python stream: pillars, then agents
-  if (lane == 0) d2d_w_seed_python(key, seed);
-  __syncthreads();
-  int p = D2D_W_BUF, attempts = 0, ok = 1;
+// d2d_worlds_build for the slots of a stream that were just handed a new episode (include/d2d_worlds_stream.h): one wave per slot,
+// and a wave whose refill byte is 0 is gone before it reads anything else.  The flags of a rebuilt slot are written here, as one
+// word: a slot that hit max_attempts is done from this launch on, so no later launch steps it.
+__global__ __launch_bounds__(WAVE) void worlds_build_masked_kernel(const d2d_world_spec s, const d2d_state st, const uint8_t *refill) {
+  if (!refill[blockIdx.x]) return;
+#include "d2d_worlds_build.inc"
+  if (st.flags && lane < 4) st.flags[(size_t)e * 4 + lane] = (uint8_t)((!ok && lane == D2D_STREAM_F_DONE) ? 1 : 0);
+}
 
-  const uint32_t pn[3] = {(uint32_t)(s.W_px - 99), (uint32_t)(s.H_px - 99), 6u};
-  const int plo[3] = {50, 50, 15};
-  int np_ = 0;
-  for (int it = 0; it < cap && ok && np_ < P; ++it) {   // every round takes at least one attempt
-    if (attempts >= cap) { ok = 0; break; }
-    attempts += 1;
-    int v[3] = {0, 0, 0};
+__device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int k = d2d_w_bit_length(pn[c]);
-      int got = 0;
-      for (int rd = 0; rd < cap && ok; ++rd) {          // every redraw counts as an attempt
-        stream_ensure(buf, p, 1, lane);
-        const uint32_t r = d2d_rng_temper(buf[p++]) >> (32 - k);
-        if (r < pn[c]) { v[c] = plo[c] + (int)r; got = 1; break; }
-        if (++attempts >= cap) ok = 0;
-      }
-      if (!got) ok = 0;
-    }
-    if (!ok) break;
-    if (d2d_w_pillar_free(v[0], v[1], v[2], par, tgt, s.pillar_clear, s.start_clear)) {
-      __syncthreads();
-      if (lane < 3) pil[3 * np_ + lane] = lane == 0 ? v[0] : lane == 1 ? v[1] : v[2];
-      __syncthreads();
-      np_ += 1;
-    }
-  }
-  if (np_ < P) ok = 0;
+  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
+  return v;
+}
 
-  int na = 0;
-  const double xw = (double)(s.W_px - 20 - 20), yw = (double)(s.H_px - 20 - 20);
-  for (int pass = 0; pass < cap && ok && na < nr; ++pass) {   // every pass takes at least one attempt
-    if (attempts >= cap) { ok = 0; break; }
-    stream_ensure(buf, p, 6, lane);
-    const int n = min(min((D2D_W_BUF - p) / 6, WAVE), cap - attempts);
-    double x = 0.0, y = 0.0, r = 0.0;
-    bool free_ = false;
-    if (lane < n) {
-      const uint32_t *g = buf + p + 6 * lane;
-      x = d2d_w_uniform(20.0, xw, d2d_rng_temper(g[0]), d2d_rng_temper(g[1]));
-      y = d2d_w_uniform(20.0, yw, d2d_rng_temper(g[2]), d2d_rng_temper(g[3]));
-      r = d2d_w_uniform(par[D2D_WE_R_LO], par[D2D_WE_R_W], d2d_rng_temper(g[4]), d2d_rng_temper(g[5]));
-      free_ = d2d_w_agent_free_static(x, y, r, par, P, pil, s.start_clear) != 0;
-      for (int q = 0; q < na; ++q)
-        if (d2d_w_norm(acc[4 * q] - x, acc[4 * q + 1] - y) <= acc[4 * q + 2] + r) free_ = false;
-    }
-    int used = n, lo = 0;
-    for (int round = 0; round < WAVE; ++round) {        // the free lanes in order: each accepted one is tested by those behind it
-      const unsigned long long m = __ballot(free_ && lane >= lo);
-      if (m == 0ull) break;
-      const int f = __ffsll((long long)m) - 1;
-      const double fx = shfl_f64(x, f), fy = shfl_f64(y, f), fr = shfl_f64(r, f);
-      if (lane == f) {
-        acc[4 * na] = x;
-        acc[4 * na + 1] = y;
-        acc[4 * na + 2] = r;
-      }
-      na += 1;
-      if (na == nr) { used = f + 1; break; }            // the words behind the attempt that completes the list stay undrawn
-      lo = f + 1;
-      if (free_ && lane > f && d2d_w_norm(fx - x, fy - y) <= fr + r) free_ = false;
-    }
-    __syncthreads();                                    // the accepted list, for the next pass
-    attempts += used;
-    p += 6 * used;
-  }
-  if (na < nr) ok = 0;
+// non-zero bytes among the low `n` (0 .. 4) bytes of w
+__device__ __forceinline__ int nonzero_bytes(uint32_t w, int n) {
+  int c = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) c += (k < n && ((w >> (8 * k)) & 0xffu)) ? 1 : 0;
+  return c;
+}
 
-  // ---- the numpy stream: seeded key, first regeneration
-  __syncthreads();
-  if (lane == 0) d2d_w_init_genrand(key, seed);
-  __syncthreads();
-  wave_regen(key, lane);
-  if (st.rng)
-    for (int i = lane; i < D2D_RNG_WORDS; i += WAVE)
-      st.rng[(size_t)e * D2D_RNG_WORDS + i] = !ok ? 0u : i < D2D_RNG_KEY ? key[i] : i == D2D_RNG_POS ? (uint32_t)D2D_W_NP_POS : 0u;
-  if (lane == 0) s.status[e] = ok ? D2D_WORLD_OK : D2D_WORLD_CAP;
-  for (int i = lane; i < 3 * P; i += WAVE) s.obstacles[(size_t)e * P * 3 + i] = ok ? pil[i] : 0;
-
-  // ---- grids before the agents: border, pillar discs; the drone's map is unexplored
+// One wave per slot: the record of a finished episode.  dmap's cells are counted a word at a time where the address allows.  Row-major:
+// an env's grid starts anywhere (W * H need not be a multiple of 4), so single bytes at the two ends, as fill_bytes writes them.
+// Tiled: an env's grid is whole tiles of 256 bytes, a word lies inside one row of one tile, and of its four cells those with j < H
+// of a row i < W count -- the padding is skipped, whatever it holds.
+__global__ __launch_bounds__(WAVE) void stream_harvest_kernel(const d2d_state st, const int32_t *slot_episode, int W, int H, int tile,
+                                                             long long M, int32_t *rows) {
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (!st.flags[(size_t)e * 4 + D2D_STREAM_F_DONE]) return;
+  const int ep = slot_episode[e];
+  if (ep < 0 || (long long)ep >= M) return;
   const int G = d2d_w_grid_bytes(W, H, tile);
-  uint8_t *gt = st.gt + (size_t)e * G;
-  fill_bytes(gt, G, lane, [&](int f) -> uint8_t {
-    int i, j;
-    return (ok && d2d_w_cell_of(f, W, H, tile, &i, &j)) ? d2d_w_static_cell(i, j, W, H, scale, P, pil) : (uint8_t)0;
-  });
-  fill_bytes(st.dmap + (size_t)e * G, G, lane, [](int) -> uint8_t { return 0; });
-  __syncthreads();   // (drains the wave's stores: the DYNAMIC cells below land behind them)
+  const uint8_t *p = st.dmap + (size_t)e * G;
+  int cnt = 0;
+  if (!tile) {
+    int head = (int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u);
+    if (head > G) head = G;
+    if (lane < head) cnt += p[lane] != 0;
+    const int nw = (G - head) >> 2;
+    const uint32_t *w = (const uint32_t *)(p + head);
+    for (int q = lane; q < nw; q += WAVE) cnt += nonzero_bytes(w[q], 4);
+    const int t0 = head + 4 * nw;
+    if (t0 + lane < G) cnt += p[t0 + lane] != 0;
+  } else {
+    const uint32_t *w = (const uint32_t *)p;        // e * G is a multiple of 256 and the field's base is a word's
+    for (int q = lane; q < (G >> 2); q += WAVE) {
+      int i, j;
+      d2d_w_cell_of(4 * q, W, H, tile, &i, &j);     // the word's first cell; the other three follow it in j
+      const int n = i < W ? min(max(H - j, 0), 4) : 0;
+      if (n) cnt += nonzero_bytes(w[q], n);
+    }
+  }
+  cnt = wave_sum(cnt);
+  if (lane < D2D_STREAM_ROW_F) {
+    const int32_t *c = st.counters + (size_t)e * D2D_CF;
+    const uint8_t *f = st.flags + (size_t)e * 4;
+    const int32_t v = lane == D2D_STREAM_R_STEPS ? c[D2D_C_STEPS] : lane == D2D_STREAM_R_SM ? c[D2D_C_SM]
+                    : lane == D2D_STREAM_R_BUF_N ? c[D2D_C_BUF_N] : lane == D2D_STREAM_R_BUF_TS ? c[D2D_C_BUF_TS]
+                    : lane == D2D_STREAM_R_DMAP ? cnt : (int32_t)f[lane - D2D_STREAM_R_FLAG0];
+    rows[(size_t)ep * D2D_STREAM_ROW_F + lane] = v;
+  }
+}
 
-  // ---- agent records, lane = agent; then each agent's disc, wave = block of cells
-  double *ag = st.agents + (size_t)e * D2D_AF * N;
-  for (int k0 = 0; k0 < N; k0 += WAVE) {
-    const int k = k0 + lane;
-    double x = 0.0, y = 0.0, r2 = 0.0;
-    int ci = 0, cj = 0, u0 = 0;
-    if (k < N) {
-      double vx, vy, r, tr;
-      if (k < nr) {
-        x = acc[4 * k]; y = acc[4 * k + 1]; r = acc[4 * k + 2]; r2 = d2d_pow2(r);
-        vx = -par[D2D_WE_SPEED] * s.unit[2 * k];
-        vy = -par[D2D_WE_SPEED] * s.unit[2 * k + 1];
-        tr = r;
+// One workgroup strides over the slots.  The exclusive scan of "harvested" is a ballot inside a wave, the waves' totals through LDS
+// inside a stride, and a carry from stride to stride: no atomics, so the assignment is a function of the flags alone.
+#define ASSIGN_BLOCK 1024
+__global__ __launch_bounds__(ASSIGN_BLOCK) void stream_assign_kernel(const uint8_t *flags, int B, long long M, uint32_t map_id0,
+                                                                    int32_t *slot_episode, uint32_t *map_id, uint8_t *refill,
+                                                                    long long *counts) {
+  __shared__ int wave_total[ASSIGN_BLOCK / WAVE];
+  const int tid = threadIdx.x, lane = tid % WAVE, wv = tid / WAVE;
+  const long long cursor = counts[0], finished = counts[1];
+  long long carry = 0;
+  for (int base = 0; base < B; base += ASSIGN_BLOCK) {
+    const int e = base + tid;
+    const bool h = e < B && flags[(size_t)e * 4 + D2D_STREAM_F_DONE] != 0 && slot_episode[e] >= 0;
+    const unsigned long long m = __ballot(h);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wv] = __popcll(m);
+    __syncthreads();
+    int below = 0, total = 0;
+    for (int k = 0; k < ASSIGN_BLOCK / WAVE; ++k) {
+      const int t = wave_total[k];
+      below += k < wv ? t : 0;
+      total += t;
+    }
+    if (e < B) {
+      if (h) {
+        const long long k = cursor + carry + below + before;
+        if (k < M) {
+          slot_episode[e] = (int32_t)k;
+          map_id[e] = map_id0 + (uint32_t)k;
+          refill[e] = 1;
+        } else {
+          slot_episode[e] = -1;
+          refill[e] = 0;
+        }
       } else {
-        const int32_t *c = s.cells + 3 * (size_t)(k - nr);
-        x = (double)(5 + c[0] * 10); y = (double)(5 + c[1] * 10); r = 5.0; r2 = 25.0;
-        vx = d2d_w_static_vel(key, c[2], par[D2D_WE_SPEED], 0);
-        vy = d2d_w_static_vel(key, c[2], par[D2D_WE_SPEED], 1);
-        tr = par[D2D_WE_TRK_R];
-      }
-      const int unit = (int)d2d_w_floordiv(r, scale);
-      ci = (int)d2d_w_floordiv(x, scale);
-      cj = (int)d2d_w_floordiv(y, scale);
-      u0 = unit + 2;
-      ag[D2D_A_PX * N + k] = ok ? x : 0.0;
-      ag[D2D_A_PY * N + k] = ok ? y : 0.0;
-      ag[D2D_A_VX * N + k] = ok ? vx : 0.0;
-      ag[D2D_A_VY * N + k] = ok ? vy : 0.0;
-      ag[D2D_A_R * N + k] = ok ? r : 0.0;
-      ag[D2D_A_R2 * N + k] = ok ? r2 : 0.0;
-      st.agent_unit[(size_t)e * N + k] = ok ? unit : 0;
-      int32_t *dp = st.dyn_prev + ((size_t)e * N + k) * 3;
-      dp[0] = ok ? ci : 0;
-      dp[1] = ok ? cj : 0;
-      dp[2] = ok ? u0 : 0;
-      s.tracker_radius[(size_t)e * N + k] = ok ? tr : 0.0;
-      st.active[(size_t)e * N + k] = 0;
-      if (st.kf_len) st.kf_len[(size_t)e * N + k] = ok ? 1 : 0;
-    }
-    const int cnt = min(WAVE, N - k0);
-    for (int a = 0; ok && a < cnt; ++a) {
-      const double ax = shfl_f64(x, a), ay = shfl_f64(y, a), ar2 = shfl_f64(r2, a);
-      const int ai = __shfl(ci, a, WAVE), aj = __shfl(cj, a, WAVE), au = __shfl(u0, a, WAVE);
-      const int side = 2 * au + 1;
-      for (int c = lane; c < side * side; c += WAVE) {
-        const int i = ai - au + c / side, j = aj - au + c % side;
-        if (i >= 0 && i < W && j >= 0 && j < H && d2d_w_in_agent(i, j, scale, ax, ay, ar2))
-          gt[d2d_w_cell_index(i, j, H, tile)] = D2D_DYNAMIC;
+        refill[e] = 0;
       }
     }
+    carry += total;
+    __syncthreads();      // wave_total is rewritten by the next stride
   }
-  if (st.kf)
-    for (int i = lane; i < N * D2D_KF; i += WAVE) st.kf[(size_t)e * N * D2D_KF + i] = ok ? d2d_w_kf_default(i % D2D_KF) : 0.0;
+  if (tid == 0) {         // every thread read counts before the first barrier; B == 0 launches nothing
+    counts[0] = cursor + carry < M ? cursor + carry : M;
+    counts[1] = finished + carry;
+  }
+}
 
-  // ---- drone, targets, counters
-  if (lane < D2D_DF) {
-    double v = 0.0;
-    if (ok) v = lane == D2D_D_X ? par[D2D_WE_X0] : lane == D2D_D_Y ? par[D2D_WE_Y0] : lane == D2D_D_YAW ? 270.0 : 0.0;   // (-90) % 360
-    st.drone[(size_t)e * D2D_DF + lane] = v;
-  }
-  if (lane < 2) st.target[(size_t)e * 2 + lane] = ok ? par[D2D_WE_X0 + lane] : 0.0;
-  for (int i = lane; i < 2 * T; i += WAVE) st.targets[(size_t)e * T * 2 + i] = ok ? tgt[i] : 0.0;
-  if (lane < D2D_CF) {
-    int v = 0;
-    if (ok) v = lane == D2D_C_SM ? D2D_SM_WAIT_FOR_GOAL : lane == D2D_C_NTGT ? (int)par[D2D_WE_NTGT] : 0;
-    st.counters[(size_t)e * D2D_CF + lane] = v;
-  }
+// Zero the rows of the refilled slots of one per-slot buffer ([B][words] of 32 bits): one workgroup per slot, gone after reading its
+// refill byte where that is 0.  For the per-slot state no masked reset covers (the trajectory storage, the search scratch, the
+// scratch half of the RVO velocities): cost follows the slots rebuilt, not the batch.
+#define CLEAR_BLOCK 256
+__global__ __launch_bounds__(CLEAR_BLOCK) void stream_clear_kernel(uint32_t *base, long long words, const uint8_t *refill) {
+  if (!refill[blockIdx.x]) return;
+  uint32_t *row = base + (size_t)blockIdx.x * (size_t)words;
+  for (long long i = threadIdx.x; i < words; i += CLEAR_BLOCK) row[i] = 0u;
 }
 
 size_t lds_bytes(const d2d_world_spec *s) {
@@ -295,6 +251,25 @@ int check_spec(const d2d_world_spec *s) {
   return 0;
 }
 
+int check_arrays(const d2d_world_spec *spec, const d2d_state *st) {
+  if (!spec->map_id || !spec->env_par || !spec->env_tgt || !spec->status || (spec->n_rand && !spec->unit) ||
+      (spec->n_cells && !spec->cells) || (spec->N && !spec->tracker_radius) || (spec->P && !spec->obstacles))
+    return fail(-1, "d2d_worlds: a spec array is NULL");
+  if (!st->gt || !st->dmap || !st->drone || !st->target || !st->targets || !st->counters ||
+      (spec->N && (!st->agents || !st->agent_unit || !st->dyn_prev || !st->active)))
+    return fail(-1, "d2d_worlds: a world field of the state is NULL");
+  return 0;
+}
+
+int launched() {
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) {
+    snprintf(g_err, sizeof g_err, "d2d_worlds: launch failed: %s", hipGetErrorString(err));
+    return -3;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -314,19 +289,54 @@ int d2d_worlds_build(const d2d_world_spec *spec, const d2d_state *st, void *stre
   if (const int rc = check_spec(spec)) return rc;
   if (!st) return fail(-1, "d2d_worlds: state is NULL");
   if (spec->B == 0) return 0;
-  if (!spec->map_id || !spec->env_par || !spec->env_tgt || !spec->status || (spec->n_rand && !spec->unit) ||
-      (spec->n_cells && !spec->cells) || (spec->N && !spec->tracker_radius) || (spec->P && !spec->obstacles))
-    return fail(-1, "d2d_worlds: a spec array is NULL");
-  if (!st->gt || !st->dmap || !st->drone || !st->target || !st->targets || !st->counters ||
-      (spec->N && (!st->agents || !st->agent_unit || !st->dyn_prev || !st->active)))
-    return fail(-1, "d2d_worlds: a world field of the state is NULL");
+  if (const int rc = check_arrays(spec, st)) return rc;
   hipLaunchKernelGGL(worlds_build_kernel, dim3((unsigned)spec->B), dim3(WAVE), lds_bytes(spec), (hipStream_t)stream, *spec, *st);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    snprintf(g_err, sizeof g_err, "d2d_worlds: launch failed: %s", hipGetErrorString(err));
-    return -3;
-  }
-  return 0;
+  return launched();
+}
+
+int d2d_worlds_build_masked(const d2d_world_spec *spec, const d2d_state *st, const uint8_t *refill, void *stream) {
+  if (const int rc = check_spec(spec)) return rc;
+  if (!st) return fail(-1, "d2d_worlds: state is NULL");
+  if (spec->B == 0) return 0;
+  if (!refill) return fail(-1, "d2d_worlds_build_masked: refill is NULL (d2d_worlds_build is the launch without a mask)");
+  if (const int rc = check_arrays(spec, st)) return rc;
+  hipLaunchKernelGGL(worlds_build_masked_kernel, dim3((unsigned)spec->B), dim3(WAVE), lds_bytes(spec), (hipStream_t)stream, *spec, *st,
+                     refill);
+  return launched();
+}
+
+int d2d_stream_harvest(const d2d_state *st, const int32_t *slot_episode, int32_t B, int32_t W, int32_t H, int32_t grid_tile, int64_t M,
+                       int32_t *rows, void *stream) {
+  if (B < 0 || W < 1 || H < 1 || M < 0 || M > D2D_STREAM_MAX_EPISODES) return fail(-1, "d2d_stream_harvest: B >= 0, W, H >= 1, 0 <= M <= D2D_STREAM_MAX_EPISODES");
+  if (grid_tile != 0 && grid_tile != 16) return fail(-1, "d2d_stream_harvest: grid_tile is 0 or 16");
+  if (((long long)(W + 15) / 16) * ((H + 15) / 16) * 256LL > 0x3fffffffLL)
+    return fail(-4, "d2d_stream_harvest: grid too large for 32-bit indices inside one env");
+  if (B == 0 || M == 0) return 0;
+  if (!st || !st->flags || !st->counters || !st->dmap || !slot_episode || !rows) return fail(-1, "d2d_stream_harvest: a pointer is NULL");
+  hipLaunchKernelGGL(stream_harvest_kernel, dim3((unsigned)B), dim3(WAVE), 0, (hipStream_t)stream, *st, slot_episode, W, H, grid_tile,
+                     (long long)M, rows);
+  return launched();
+}
+
+int d2d_stream_assign(const uint8_t *flags, int32_t B, int64_t M, uint32_t map_id0, int32_t *slot_episode, uint32_t *map_id,
+                      uint8_t *refill, int64_t *counts, void *stream) {
+  if (B < 0 || M < 0 || M > D2D_STREAM_MAX_EPISODES) return fail(-1, "d2d_stream_assign: B >= 0, 0 <= M <= D2D_STREAM_MAX_EPISODES");
+  if ((unsigned long long)map_id0 + (unsigned long long)M > 0x100000000ULL) return fail(-1, "d2d_stream_assign: map_id0 + M > 2^32");
+  if (B == 0) return 0;
+  if (!flags || !slot_episode || !map_id || !refill || !counts) return fail(-1, "d2d_stream_assign: a pointer is NULL");
+  hipLaunchKernelGGL(stream_assign_kernel, dim3(1), dim3(ASSIGN_BLOCK), 0, (hipStream_t)stream, flags, B, (long long)M, map_id0,
+                     slot_episode, map_id, refill, (long long *)counts);
+  return launched();
+}
+
+int d2d_stream_clear(void *base, int64_t bytes_per_slot, const uint8_t *refill, int32_t B, void *stream) {
+  if (B < 0 || bytes_per_slot < 0 || (bytes_per_slot & 3) || ((uintptr_t)base & 3u))
+    return fail(-1, "d2d_stream_clear: B >= 0, bytes_per_slot a multiple of 4 and >= 0, base aligned to 4 bytes");
+  if (B == 0 || bytes_per_slot == 0) return 0;
+  if (!base || !refill) return fail(-1, "d2d_stream_clear: a pointer is NULL");
+  hipLaunchKernelGGL(stream_clear_kernel, dim3((unsigned)B), dim3(CLEAR_BLOCK), 0, (hipStream_t)stream, (uint32_t *)base,
+                     (long long)(bytes_per_slot >> 2), refill);
+  return launched();
 }
 
 }  // extern "C"

@@ -60,25 +60,41 @@ class Experiment:
         return row
 
 
-def batch_rows(params, env):
-    """One tuple per env of VecDrone2DEnv `env` with the columns of experiment.py:73-103, read off the state as its episodes left it."""
-    p, s = params, env.state
+def batch_records(env):
+    """[B, 8] int64 numpy: per env the numbers its CSV row is made of, in the columns of include/d2d_worlds_stream.h
+    (D2D_STREAM_R_*): C_STEPS, C_SM, C_BUF_N, C_BUF_TS, flags[0..2] and the number of non-zero cells of dmap -- what
+    d2d_stream_harvest records for a finished slot."""
+    s = env.state
     c = s.counters.cpu().numpy()
     f = s.flags.cpu().numpy()
     disc = (s.dmap != 0).flatten(1).sum(1).cpu().numpy()
-    out = []
-    for e in range(env.num_envs):
-        n = int(c[e, A.C_BUF_N])
-        tracking_time = float(c[e, A.C_BUF_TS]) * 0.1
-        with np.errstate(divide='ignore', invalid='ignore'):
-            mean_time = np.float64(tracking_time) / n if n else float('nan')
-        sm = int(c[e, A.C_SM])
-        out.append((p.gaze_method, p.planner, p.motion_profile, p.map_id + env.env_offset + e, p.agent_radius,
-                    p.agent_number, p.pillar_number, p.agent_max_speed, p.drone_max_speed, p.var_cam, p.init_position,
-                    p.target_list[0], int(c[e, A.C_STEPS]) * p.dt, int(disc[e]), n, mean_time,
-                    1 if sm == A.SM_GOAL_REACHED else 0, 1 if f[e, 0] == 1 else 0, 1 if f[e, 0] == 2 else 0,
-                    int(f[e, 2]), int(f[e, 1]), sm))
+    out = np.zeros((env.num_envs, A.STREAM_ROW_F), dtype=np.int64)
+    out[:, [A.STREAM_R_STEPS, A.STREAM_R_SM, A.STREAM_R_BUF_N, A.STREAM_R_BUF_TS]] = c[:, [A.C_STEPS, A.C_SM, A.C_BUF_N, A.C_BUF_TS]]
+    out[:, A.STREAM_R_FLAG0:A.STREAM_R_FLAG0 + 3] = f[:, :3]
+    out[:, A.STREAM_R_DMAP] = disc
     return out
+
+
+def record_row(params, map_id, rec):
+    """The tuple with the columns of experiment.py:73-103 of one record (batch_records / d2d_stream_harvest) of the world `map_id`."""
+    p = params
+    n = int(rec[A.STREAM_R_BUF_N])
+    tracking_time = float(rec[A.STREAM_R_BUF_TS]) * 0.1
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean_time = np.float64(tracking_time) / n if n else float('nan')
+    sm = int(rec[A.STREAM_R_SM])
+    f = rec[A.STREAM_R_FLAG0:A.STREAM_R_FLAG0 + 3]
+    return (p.gaze_method, p.planner, p.motion_profile, map_id, p.agent_radius,
+            p.agent_number, p.pillar_number, p.agent_max_speed, p.drone_max_speed, p.var_cam, p.init_position,
+            p.target_list[0], int(rec[A.STREAM_R_STEPS]) * p.dt, int(rec[A.STREAM_R_DMAP]), n, mean_time,
+            1 if sm == A.SM_GOAL_REACHED else 0, 1 if f[0] == 1 else 0, 1 if f[0] == 2 else 0,
+            int(f[2]), int(f[1]), sm)
+
+
+def batch_rows(params, env):
+    """One tuple per env of VecDrone2DEnv `env` with the columns of experiment.py:73-103, read off the state as its episodes left it."""
+    rec = batch_records(env)
+    return [record_row(params, params.map_id + env.env_offset + e, rec[e]) for e in range(env.num_envs)]
 
 
 class _BatchRows:
@@ -115,6 +131,16 @@ class ExperimentBatch(_BatchRows):
 
     def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_gaze=True, device_worlds=False):
         from .vec_env import VecDrone2DEnv, build_worlds
+        p, self._host_lookahead = self.accepted(params, backend, device_gaze)
+        self.params = p
+        worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
+        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
+                                 device_plugins=True, gaze='external' if self._host_lookahead else p.gaze_method)
+        self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
+
+    @staticmethod
+    def accepted(params, backend=None, device_gaze=True):
+        """(the Params this runner plays, does LookAhead run from the host?), or the runner's refusal"""
         from ._lib import HipBackend
         p = with_defaults(params)
         if p.planner == 'Jerk_Primitive':
@@ -136,14 +162,10 @@ class ExperimentBatch(_BatchRows):
         if p.gaze_method == 'Owl' and not getattr(backend if backend is not None else HipBackend, 'supports_device_owl_gaze', False):
             raise NotImplementedError('ExperimentBatch: Owl needs a backend with the device Owl stage (use Experiment with the host '
                                       'policy gaze.Owl, one episode at a time)')
-        self._host_lookahead = p.gaze_method == 'LookAhead' and not device_heading
+        host_lookahead = p.gaze_method == 'LookAhead' and not device_heading
         if p.gaze_method == 'NoControl':
             p.drone_view_range = 360                                   # experiment.py:28-29
-        self.params = p
-        worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
-        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
-                                 device_plugins=True, gaze='external' if self._host_lookahead else p.gaze_method)
-        self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
+        return p, host_lookahead
 
     def _lookahead_actions(self):
         """yaw_planner.LookAhead.plan for every env (gaze.LookAhead, vectorised over the batch on the host): the path of a
@@ -200,6 +222,16 @@ class SteppedExperimentBatch(_BatchRows):
 
     def __init__(self, params, num_envs, device='cuda:0', backend=None, workers=0, device_worlds=False, jerk_tie=None):
         from .vec_env import VecDrone2DEnv, build_worlds
+        self.params = p = self.accepted(params, backend)
+        worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
+        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
+                                 device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie)
+        self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
+        self.steps_run = 0
+
+    @staticmethod
+    def accepted(params, backend=None):
+        """the Params this runner plays, or the runner's refusal"""
         from ._lib import HipBackend
         p = with_defaults(params)
         primitive_rvo = p.planner == 'Primitive' and p.motion_profile == 'RVO'     # each (planner, profile) cell has one batch runner
@@ -218,14 +250,62 @@ class SteppedExperimentBatch(_BatchRows):
             raise NotImplementedError("SteppedExperimentBatch needs a backend with the step path's gaze launch (include/d2d_gaze.h)")
         if p.gaze_method == 'NoControl':
             p.drone_view_range = 360                                   # experiment.py:28-29
-        self.params = p
-        worlds = 'device' if device_worlds else build_worlds(p, num_envs, workers=workers)
-        self.env = VecDrone2DEnv(p, num_envs, device=device, backend=backend, planner=p.planner, worlds=worlds,
-                                 device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie)
-        self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1           # freezing ends every episode by then
-        self.steps_run = 0
+        return p
 
     def run(self, check_every=16):
         self.steps_run = self.env.run_episodes(self.max_steps, check_every)
         self.env.sync()
         return self.rows()
+
+
+class EpisodeStream:
+    """`num_episodes` seeded episodes (map ids `map_id + 0 .. map_id + num_episodes - 1`) streamed through `slots` resident envs
+    (VecDrone2DEnv.stream_episodes): a slot whose episode has ended is handed the next map id and rebuilt in place on the device
+    (include/d2d_worlds_stream.h), so memory is bounded by the slots and no slot waits for the slowest episode of a batch.
+
+    The env is the one the batch runner of `params`' cell would build with device worlds -- ExperimentBatch's for Primitive / NoMove
+    under CVM (the persistent closed loop), SteppedExperimentBatch's for Jerk_Primitive and for Primitive under RVO -- and that
+    runner's refusals hold here.  `rows()` are its rows: an episode depends on nothing but its world, so neither the slot that
+    played it nor `refill_every` can change its row, and the rows come out in episode order.  An episode whose world could not be
+    placed (column 0 of its record == STREAM_BUILD_FAILED, `build_failed` lists their map ids) has a row of zeros."""
+
+    def __init__(self, params, num_episodes, slots, device='cuda:0', backend=None, jerk_tie=None):
+        from .vec_env import VecDrone2DEnv
+        p = with_defaults(params)
+        stepped = p.planner == 'Jerk_Primitive' or (p.planner == 'Primitive' and p.motion_profile == 'RVO')
+        if stepped:
+            p = SteppedExperimentBatch.accepted(p, backend)
+        else:
+            p, host_lookahead = ExperimentBatch.accepted(p, backend)
+            if host_lookahead:
+                raise NotImplementedError('EpisodeStream: LookAhead needs a backend with the device LookAhead / LookGoal stage (a '
+                                          'streamed episode has no host policy); ExperimentBatch drives it from the host')
+        self.params, self.num_episodes = p, int(num_episodes)
+        self.env = VecDrone2DEnv(p, int(slots), device=device, backend=backend, planner=p.planner, worlds='device',
+                                 device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie if stepped else None)
+        self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1
+        self.steps_run = 0
+        self.records = None
+
+    def run(self, refill_every=64, **kw):
+        if self.records is not None:
+            raise RuntimeError('EpisodeStream.run(): this stream has run, and its slots hold the last worlds that passed through them; '
+                               'rows() returns its rows again, a new EpisodeStream runs the episodes again')
+        self.records = self.env.stream_episodes(self.num_episodes, refill_every, **kw).cpu().numpy()
+        self.steps_run = self.env.steps_streamed
+        return self.rows()
+
+    @property
+    def build_failed(self):
+        """map ids of the episodes whose world hit max_attempts"""
+        m0 = self.params.map_id + self.env.env_offset
+        return [m0 + int(k) for k in np.nonzero(self.records[:, A.STREAM_R_STEPS] == A.STREAM_BUILD_FAILED)[0]]
+
+    def rows(self):
+        """One tuple per episode, in episode order, with the columns of experiment.py:73-103."""
+        if self.records is None:
+            raise RuntimeError('EpisodeStream.rows(): run() first')
+        m0 = self.params.map_id + self.env.env_offset
+        return [record_row(self.params, m0 + k, self.records[k]) for k in range(self.num_episodes)]
+
+    write_csv = _BatchRows.write_csv

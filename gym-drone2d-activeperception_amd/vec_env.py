@@ -267,6 +267,9 @@ class VecDrone2DEnv:
             T = worlds[0]['T'] if worlds else 1
             if any(w['N'] != N for w in worlds):
                 raise ValueError('all envs of a batch must have the same number of agents')
+        self._world_inp = inp if on_device and dw is None else None     # what stream_episodes() rebuilds a slot's world from
+        self._streamed = False
+        self._own_noise = False
         self.cfg = host_init.derive_cfg(self.params, B=self.num_envs, N=N, T=T, planner_mode=self.planner_mode,
                                         kf_enabled=kf_enabled, grid_tile=_grid_tile(self.params, backend, grid_layout))
         self.state = BatchState(self.cfg, self.device)
@@ -305,6 +308,7 @@ class VecDrone2DEnv:
         self.jerk = None
         self.gaze_state = None             # gaze_plugin.GazeState: LookAhead / Owl as a launch in front of the step
         self.step_gaze = None              # the gaze policy the step path evaluates itself (policy_step, run_episodes), or None
+        self.device_gaze = None            # the gaze policy the device evaluates in whichever loop runs the episodes, or None
         if device_plugins and planner == 'Jerk_Primitive':
             # its own library and its own per-batch state (jerk_plugin.JerkState): no d2d_plan is involved
             # LookAhead / Owl: a launch of libd2d_gaze.so in front of the step (include/d2d_gaze.h), on a backend that has it.
@@ -333,7 +337,7 @@ class VecDrone2DEnv:
                 from .gaze_plugin import GazeState
                 self.gaze_state = GazeState(self.params, self.cfg, self.device, gaze)
                 self._gaze_call = self.gaze_state.call(self.state)
-            self.step_gaze = gaze if gaze not in ('external', None) else None
+            self.step_gaze = self.device_gaze = gaze if gaze not in ('external', None) else None
         elif device_plugins:
             from .device_plugins import PluginState
             gaze = gaze if gaze is not None else self.params.gaze_method
@@ -366,6 +370,7 @@ class VecDrone2DEnv:
             # the step path's episode loop (policy_step, run_episodes) takes the Primitive plugins with a policy of their own
             if planner == 'Primitive' and gaze not in ('external', None):
                 self.step_gaze = gaze
+            self.device_gaze = gaze if gaze not in ('external', None) else None
 
     # ------------------------------------------------------------------ gym-like surface (batched)
     @property
@@ -374,6 +379,9 @@ class VecDrone2DEnv:
 
     def reset(self, mask=None):
         """envs/drone_v2.py:259-261: back to the seeded initial world (all envs, or those in `mask`)."""
+        if self._streamed:
+            raise RuntimeError('reset(): this env has streamed episodes (stream_episodes), so its slots hold other worlds than its '
+                               'snapshot; build a new VecDrone2DEnv for the map ids you want')
         if mask is not None:
             mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
         self.backend.reset(self.cfg, self._st, self._init_st, mask)
@@ -521,30 +529,36 @@ class VecDrone2DEnv:
                     break
             return t
         live = self._jerk_live(live)
-        noise = self.state.noise if self.cfg.noise_rows > 1 else None
-        perceive = A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE
         t = 0
+        while t < n and self.num_envs:
+            self._jerk_step(live)
+            t += 1
+            if t % every == 0 and t < n and bool(self.state.flags[:, A.F_DONE].all()):
+                break
+        return t
+
+    def _jerk_step(self, live):
+        """One step of the episode loop with planner='Jerk_Primitive' (run_episodes, stream_episodes): d2d_gaze_act, under RVO the two
+        RVO launches, d2d_run_stages(PERCEIVE | SKIP_DONE) with this step's row of the noise, the plan, d2d_run_stages(ACT |
+        SKIP_DONE).  `live`: the plan and RVO launches that leave finished envs alone (include/d2d_jerk_live.h, d2d_rvo_live.h),
+        else the unmasked ones"""
+        noise = self.state.noise if self.cfg.noise_rows > 1 else None
         try:
-            while t < n and self.num_envs:
-                self.run_gaze()
-                if noise is not None:                 # as rollout(): a single d2d_run_stages reads the block's first row
-                    self._st.noise = noise[self.cfg.noise_row0].data_ptr()
-                if self.rvo:
-                    self._rvo_agents_live() if live else self._rvo_agents()
-                self.backend.run_stages(self.cfg, self._st, perceive | A.ST_SKIP_DONE)
-                if live:
-                    self.backend.jerk_plan_live(self._jerk_call, self.state.flags)
-                else:
-                    self.run_jerk_plan()
-                self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
-                self._advance_noise(1)
-                t += 1
-                if t % every == 0 and t < n and bool(self.state.flags[:, A.F_DONE].all()):
-                    break
+            self.run_gaze()
+            if noise is not None:                     # as rollout(): a single d2d_run_stages reads the block's first row
+                self._st.noise = noise[self.cfg.noise_row0].data_ptr()
+            if self.rvo:
+                self._rvo_agents_live() if live else self._rvo_agents()
+            self.backend.run_stages(self.cfg, self._st, (A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE) | A.ST_SKIP_DONE)
+            if live:
+                self.backend.jerk_plan_live(self._jerk_call, self.state.flags)
+            else:
+                self.run_jerk_plan()
+            self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
+            self._advance_noise(1)
         finally:
             if noise is not None:
                 self._st.noise = noise.data_ptr()
-        return t
 
     def run_jerk_plan(self):
         """d2d_jerk_plan for every env: plan_ok / wp_valid / wp of this step, from what d2d_perceive left"""
@@ -592,6 +606,7 @@ class VecDrone2DEnv:
         rows = n.shape[0] if n.dim() == 4 else 1
         n = n.reshape(rows, self.num_envs, self.cfg.N, 2).to(self.device).contiguous()
         self.state.noise = n
+        self._own_noise = True
         self._st.noise = n.data_ptr()
         self.cfg.noise_rows = rows
         self.cfg.noise_row0 = 0
@@ -709,6 +724,156 @@ class VecDrone2DEnv:
                 'tracked_agent': s.counters[:, A.C_TRACKED], 'newly_tracked': s.newly, 'hit': s.hit}
         return obs, self.reward, done, info
 
+    # ------------------------------------------------------------------ a stream of seeded episodes over the resident slots
+    def _needs_stream(self, num_episodes):
+        backend_for(self.backend, None, 'supports_device_worlds', 'has no device world construction, which stream_episodes() rebuilds '
+                    'a finished slot with: run the episodes as batches (runner.ExperimentBatch / SteppedExperimentBatch)')
+        backend_for(self.backend, None, 'supports_episode_stream', 'has no launches that refill a finished slot '
+                    '(include/d2d_worlds_stream.h): run the episodes as batches (runner.ExperimentBatch / SteppedExperimentBatch)')
+        if self._streamed:
+            raise RuntimeError('stream_episodes(): this env has streamed episodes already, so its slots hold the last worlds that '
+                               'passed through them, not map ids map_id + 0 ..; build a new VecDrone2DEnv / EpisodeStream for another run')
+        if self._world_inp is None:
+            raise NotImplementedError("stream_episodes(): the worlds of this env were built on the host or handed over; a finished slot "
+                                      "is rebuilt on the device from its map id, so build the env with worlds='device'")
+        if self._own_noise:
+            raise NotImplementedError('stream_episodes(): set_noise() rows belong to the envs they were drawn for, not to the episodes '
+                                      'that pass through a slot; leave the draws to the device (var_cam != 0 on a backend with '
+                                      'supports_device_noise) or run the episodes as batches')
+        if self.cfg.sigma != 0.0 and not self.device_noise:
+            raise NotImplementedError('stream_episodes(): var_cam != 0 needs a backend that draws the measurement noise on the device '
+                                      '(supports_device_noise); run the episodes as batches with set_noise()')
+        if self.device_gaze is None or (self.plugins is None and self.jerk is None):
+            raise RuntimeError('stream_episodes() needs device_plugins=True and a gaze policy the device evaluates '
+                               "(not gaze='external'); step the env yourself for anything else")
+        if self.plugins is not None and self.rvo:
+            self._needs_step_gaze('stream_episodes()')
+        if self.jerk is not None and not self._jerk_live(None):
+            self._jerk_live(True)              # raises, naming the launch that is missing
+        M = int(num_episodes)
+        m0 = self.params.map_id + self.env_offset
+        if M < 0 or M > A.STREAM_MAX_EPISODES:
+            raise ValueError(f'stream_episodes(): {M} episodes: 0 <= num_episodes <= {A.STREAM_MAX_EPISODES}')
+        if m0 + M > 2 ** 32:
+            raise ValueError(f'stream_episodes(): map_id {m0} + {M} episodes passes 2**32: numpy seeds with 0 <= map_id < 2**32 only; '
+                             'split the run into streams that end below it')
+        if self.num_envs and M and bool(self.state.counters[:, A.C_STEPS].ne(0).any() | self.state.flags.ne(0).any()):
+            # (one host read before the first step: the first min(B, M) episodes are the envs as constructed)
+            raise RuntimeError('stream_episodes(): this env has been stepped, and the first episodes of a stream are the envs as '
+                               'constructed; reset() it, or build a new VecDrone2DEnv / EpisodeStream')
+        return M, m0
+
+    def _episode_steps(self, n):
+        """`n` steps of the env's own episode loop, finished envs left alone: closed_loop(freeze_done=True) where closed_loop() runs,
+        the step sequences of run_episodes() elsewhere"""
+        if self.plugins is not None and not self.rvo:
+            self.closed_loop(n, freeze_done=True)
+        elif self.plugins is not None:
+            for _ in range(n):
+                self._plugins_step()
+        else:
+            for _ in range(n):
+                self._jerk_step(True)
+
+    def _refill_rest(self, refill):
+        """Everything outside the world of the slots in `refill` ([B] uint8) as a fresh env has it: the masked resets of the plugin,
+        Jerk_Primitive and gaze state (which read the tracker radii the build just wrote), and masked fills for the per-step
+        outputs.  The flags were written by the build.  No host read"""
+        s, m = self.state, refill.bool()
+        for name in ('plan_ok', 'wp_valid', 'wp', 'hit', 'newly', 'obs_local', 'obs_yaw', 'rng_draws'):
+            t = s.t.get(name)
+            if t is not None and t.numel():
+                t.masked_fill_(m.view((-1,) + (1,) * (t.dim() - 1)), 0)
+        s.action.masked_fill_(m, 1.0 if self.device_gaze == 'Rotating' else 0.0)
+        if self.rvo:                           # state.init_rvo: zero for the seeded agents, the preferred velocity for the static map's
+            k = min(int(self.params.agent_number), self.cfg.N)
+            vel = s.agent_vel
+            vel[:, :, :k].masked_fill_(m[:, None, None], 0)
+            vel[:, :, k:] = torch.where(m[:, None, None], s.agents[:, A.A_VX:A.A_VY + 1, k:], vel[:, :, k:])
+        if self.plugins is not None:
+            self.plugins.t['plan_stat'].masked_fill_(m[:, None], 0)
+        # per-slot storage that no reset covers, zero in a fresh env: the trajectory and its boxes (dead beyond the header, which
+        # d2d_plan_reset clears), the search's nodes and hash, the scratch half of the velocity swap.  d2d_stream_clear touches the
+        # refilled slots alone, so the cost follows the slots rebuilt and not the batch
+        for t in ([self.plugins.t[k] for k in ('traj', 'traj_box', 'nodes', 'hash')] if self.plugins is not None else []) + \
+                ([s.agent_vel_out] if self.rvo else []):
+            self.backend.stream_clear(t, refill)
+        if self.jerk is not None:
+            for name in ('choice', 'stat'):
+                self.jerk.t[name].masked_fill_(m, 0)
+        self.reset_plugins(refill)
+
+    def stream_episodes(self, num_episodes, refill_every=64, max_attempts=None, trace=None):
+        """Episodes map_id + 0 .. map_id + num_episodes - 1 over the env's `num_envs` slots: a slot whose episode has ended is
+        handed the next map id, its world is rebuilt in place on the device and everything that hangs on it is put back, so the
+        slots stay full while the queue lasts and memory is bounded by the slots, not the episodes.  Returns the records
+        [num_episodes, 8] int32 (include/d2d_worlds_stream.h D2D_STREAM_R_*; runner.EpisodeStream makes CSV rows of them).
+
+        The first min(num_envs, num_episodes) episodes are the envs as constructed.  Every `refill_every` steps of the env's own
+        episode loop (closed_loop(refill_every, freeze_done=True) where closed_loop() runs, the step sequences of run_episodes()
+        elsewhere) come d2d_stream_harvest, d2d_stream_assign, d2d_worlds_build_masked and the masked resets; the 8 bytes of
+        `finished` read back after the assignment are the loop's only synchronisation, and where they have not moved nothing was
+        harvested and the build and the resets, which would all be no-ops, are not queued.  An episode depends on nothing but its
+        world, so its record does not depend on `refill_every` or on the slot that played it.
+
+        A world that cannot be placed within `max_attempts` (default: the constructor's) ends at once with column 0 of its record
+        == STREAM_BUILD_FAILED.  `trace`: a list that receives (steps so far, slots live) per refill, for measurement (one more
+        host read each).  The env has then played other worlds than its snapshot: reset() refuses afterwards."""
+        for _ in self.stream_rounds(num_episodes, refill_every, max_attempts, trace):
+            pass
+        return self.stream_rows
+
+    def stream_rounds(self, num_episodes, refill_every=64, max_attempts=None, trace=None):
+        """stream_episodes() as a generator that hands control back after every refill that rebuilt a slot: yields (episodes finished,
+        the refill bytes [B] uint8 of the round); the records so far are `stream_rows`.  For callers that look at the slots in
+        between (the tests do)."""
+        M, m0 = self._needs_stream(num_episodes)
+        B, dev, s = self.num_envs, self.device, self.state
+        every = max(1, int(refill_every))
+        self.stream_rows = rows = torch.full((M, A.STREAM_ROW_F), -1, dtype=torch.int32, device=dev)
+        self.steps_streamed = 0
+        if M == 0 or B == 0:
+            return
+        inp = dict(self._world_inp)
+        if max_attempts is not None:
+            inp['max_attempts'] = int(max_attempts)
+        up = {n: torch.from_numpy(inp[n]).to(dev) for n in ('unit', 'cells', 'env_par', 'env_tgt')}
+        up['map_id'] = torch.from_numpy(inp['map_id'].view(np.int32).copy()).to(dev)
+        up['status'] = torch.zeros(B, dtype=torch.int32, device=dev)
+        N, P = self.cfg.N, inp['P']
+        radius0 = self.plugins.trk_radius0 if self.plugins is not None else self.jerk.trk_radius0     # [B, max(N, 1)]: the output's shape for N > 0
+        up['tracker_radius'] = radius0
+        up['obstacles'] = s.pillars if self.rvo else torch.zeros((B, P, 3), dtype=torch.int32, device=dev)
+        spec = world_spec(inp, self.cfg.grid_tile, lambda n: up[n].data_ptr() if up[n].numel() else s._dummy.data_ptr())
+        slot_episode = torch.arange(B, dtype=torch.int32, device=dev)
+        refill = torch.zeros(B, dtype=torch.uint8, device=dev)
+        counts = torch.tensor([min(B, M), 0], dtype=torch.int64, device=dev)
+        if M < B:                              # the surplus slots are retired before the first step
+            slot_episode[M:] = -1
+            s.flags[M:, A.F_DONE] = 1
+        self._streamed = True
+        self._stream_keep = (up, slot_episode, refill, counts)            # (the launches are asynchronous: the arrays outlive them)
+        finished, guard = 0, (-(-M // B) + 1) * (int(np.ceil(self.params.max_flight_time / self.params.dt)) + 1 + every)
+        while finished < M:
+            if self.steps_streamed > guard:
+                raise RuntimeError(f'stream_episodes(): {finished} of {M} episodes after {self.steps_streamed} steps: an episode did not end')
+            self._episode_steps(every)
+            self.steps_streamed += every
+            self.backend.stream_harvest(self.cfg, self._st, slot_episode, rows)
+            self.backend.stream_assign(s.flags, M, m0, slot_episode, up['map_id'], refill, counts)
+            now = int(counts[1])               # the only host read
+            if trace is not None:
+                trace.append((self.steps_streamed, int((s.flags[:, A.F_DONE] == 0).sum()) + int(refill.sum())))
+            if now == finished:
+                continue
+            finished = now
+            if finished >= M:                  # the queue is dry and every slot retired: nothing to rebuild
+                break
+            self.backend.build_worlds_masked(spec, self._st, refill)
+            self._refill_rest(refill)
+            yield finished, refill
+        self.sync()
+
     def closed_loop(self, nsteps=1, auto_reset=False, freeze_done=False):
         """`nsteps` reference-style steps with the plugins on the device: a = Oxford.plan(info); perceive;
         Primitive.replan_check + plan; act (experiment.py:68-70).  `auto_reset`: an env whose episode ended restarts
@@ -726,6 +891,9 @@ class VecDrone2DEnv:
                                       'lives in libd2d_rvo.so); step the env with step() / perceive() + act(), or run episodes '
                                       'through runner.Experiment.  run_episodes() / runner.SteppedExperimentBatch play whole '
                                       'episodes under this profile as a batch')
+        if auto_reset and self._streamed:
+            raise RuntimeError('closed_loop(auto_reset=True): this env has streamed episodes (stream_episodes), so its slots hold other '
+                               'worlds than the snapshot an auto reset restores; build a new VecDrone2DEnv for the map ids you want')
         mode = A.DONE_RESET if auto_reset else (A.DONE_FREEZE if freeze_done else A.DONE_CONTINUE)
         self.backend.closed_loop(self.cfg, self._st, self._plan, int(nsteps), mode,
                                  self._init_st if auto_reset else None)
