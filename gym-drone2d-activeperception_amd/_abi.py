@@ -124,7 +124,7 @@ ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_sta
 # ---- include/d2d_worlds.h: the world construction on the device (csrc/worlds/libd2d_worlds.so, its own version) ----
 D2D_WORLDS_VERSION = 1
 WORLDS_ENV_F = 8
-WE_R_LO, WE_R_W, WE_SPEED, WE_TRK_R, WE_X0, WE_Y0, WE_NTGT = range(7)
+WE_R_LO, WE_R_W, WE_SPEED, WE_TRK_R, WE_X0, WE_Y0, WE_NTGT, WE_REDRAW = range(8)
 WORLDS_MAX_ATTEMPTS = 65536
 WORLD_OK, WORLD_CAP = 0, 1
 WORLD_SPEC_INT_FIELDS = ('version', 'B', 'N', 'n_rand', 'n_cells', 'P', 'T', 'W_px', 'H_px', 'scale', 'W', 'H', 'grid_tile',
@@ -171,6 +171,18 @@ def bind_worlds_stream(lib):
         'stream_clear': (C.c_int, [V, C.c_int64, V, I, V]),
     }
     return _bind(lib, 'd2d_', sig, STREAM_ENTRY_POINTS)
+
+
+# include/d2d_worlds_table.h: the assignment of a stream whose episodes are the rows of a table
+TABLE_ENTRY_POINTS = ('stream_assign_table',)
+
+
+def bind_worlds_table(lib):
+    """argtypes / restypes of include/d2d_worlds_table.h on the loaded libd2d_worlds.so: an addition to that library, looked up as
+    an optional symbol (a build without it binds nothing here, and its version is the same)."""
+    V, I = C.c_void_p, C.c_int32
+    sig = {'stream_assign_table': (C.c_int, [V, I, C.c_int64, I, V, V, V, V, V, V, V, V, V, V])}
+    return _bind(lib, 'd2d_', sig, TABLE_ENTRY_POINTS)
 
 
 # ---- include/d2d_metrics.h: the difficulty metrics on the device (csrc/metrics/libd2d_metrics.so, its own version) ----

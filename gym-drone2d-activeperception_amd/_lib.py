@@ -125,6 +125,7 @@ class HipBackend:
         self.lib, self.fn = load_library()
         self.wlib, self.wfn = load_worlds_library()
         self.sfn = A.bind_worlds_stream(self.wlib)                        # include/d2d_worlds_stream.h, where the build has it
+        self.sfn.update(A.bind_worlds_table(self.wlib))                   # include/d2d_worlds_table.h, likewise
         self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
         self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
         self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
@@ -211,9 +212,16 @@ class HipBackend:
         Optional symbols of libd2d_worlds.so: true where the built library has all of them"""
         return all(n in self.sfn for n in A.STREAM_ENTRY_POINTS)
 
+    @property
+    def supports_episode_table(self):
+        """include/d2d_worlds_table.h: the assignment that hands a finished slot a row of an episode table
+        (stream_episodes(episodes=...)).  An optional symbol of libd2d_worlds.so: true where the built library has it"""
+        return all(n in self.sfn for n in A.TABLE_ENTRY_POINTS)
+
     def _stream_fn(self, name, *args):
         if name not in self.sfn:
-            raise D2DError(f'{WORLDS_LIB_PATH} has no d2d_{name} (include/d2d_worlds_stream.h): rebuild it with csrc/worlds/build.sh')
+            header = 'd2d_worlds_table.h' if name in A.TABLE_ENTRY_POINTS else 'd2d_worlds_stream.h'
+            raise D2DError(f'{WORLDS_LIB_PATH} has no d2d_{name} (include/{header}): rebuild it with csrc/worlds/build.sh')
         _check(self.sfn[name](*args, self._stream()), self.wfn, 'd2d_worlds')
 
     def stream_harvest(self, cfg, st, slot_episode, rows):
@@ -226,6 +234,13 @@ class HipBackend:
         retire; counts [2] int64 = (cursor, finished) moves on"""
         self._stream_fn('stream_assign', flags.data_ptr(), slot_episode.shape[0], int(num_episodes), int(map_id0), slot_episode.data_ptr(),
                         map_id.data_ptr(), refill.data_ptr(), counts.data_ptr())
+
+    def stream_assign_table(self, flags, ep_map_id, ep_par, ep_tgt, slot_episode, map_id, env_par, env_tgt, refill, counts):
+        """d2d_stream_assign_table: stream_assign for a table of episodes -- a slot that gets episode k copies ep_map_id[k] ([M] uint32
+        bits), ep_par[k] ([M, 8] float64) and ep_tgt[k] ([M, T, 2] float64) into its map_id, env_par and env_tgt"""
+        self._stream_fn('stream_assign_table', flags.data_ptr(), slot_episode.shape[0], ep_map_id.shape[0], env_tgt.shape[1],
+                        ep_map_id.data_ptr(), ep_par.data_ptr(), ep_tgt.data_ptr(), slot_episode.data_ptr(), map_id.data_ptr(),
+                        env_par.data_ptr(), env_tgt.data_ptr(), refill.data_ptr(), counts.data_ptr())
 
     def build_worlds_masked(self, spec, st, refill):
         """d2d_worlds_build_masked: build_worlds for the slots with refill [B] uint8 set, nothing of any other slot"""

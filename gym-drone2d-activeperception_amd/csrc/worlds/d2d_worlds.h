@@ -87,6 +87,15 @@ D2D_WORLDS_QUAL int d2d_w_bit_length(uint32_t n) {
 /* a + (b - a) * random() from the two tempered words of random(); w = b - a */
 D2D_WORLDS_QUAL double d2d_w_uniform(double a, double w, uint32_t g0, uint32_t g1) { return a + w * d2d_rng_double(g0, g1); }
 
+/* validation_speed.py:136-138 for one agent: the preferred velocity from the four tempered words of two random().  The
+ * arithmetic is the script's, operand for operand: random() * 40 + 20, random() * 2 * np.pi, vel * np.cos / np.sin(angle) */
+D2D_WORLDS_QUAL void d2d_w_redraw(uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3, double *pvx, double *pvy) {
+  const double vel = d2d_rng_double(g0, g1) * 40.0 + 20.0;
+  const double angle = (d2d_rng_double(g2, g3) * 2.0) * 3.141592653589793;
+  *pvx = vel * d2d_cos(angle);
+  *pvy = vel * d2d_sin(angle);
+}
+
 /* numpy.linalg.norm of a 2-vector: sqrt(x . x) */
 D2D_WORLDS_QUAL double d2d_w_norm(double dx, double dy) { return sqrt(dx * dx + dy * dy); }
 
@@ -235,6 +244,14 @@ D2D_WORLDS_QUAL void d2d_worlds_build_seq_env(const d2d_world_spec *s, const d2d
       na += 1;
     }
   }
+  /* the redraw (D2D_WE_REDRAW): the stream goes on where the last agent left it, before its key makes room for numpy's */
+  const int redraw = ok && par[D2D_WE_REDRAW] != 0.0;
+  double *ag = st->agents + (size_t)e * D2D_AF * N;
+  for (int k = 0; redraw && k < N; ++k) {
+    uint32_t g[4];
+    for (int c = 0; c < 4; ++c) D2D_W_NEXT(g[c]);
+    d2d_w_redraw(g[0], g[1], g[2], g[3], &ag[D2D_A_VX * N + k], &ag[D2D_A_VY * N + k]);
+  }
 #undef D2D_W_NEXT
   /* the numpy stream: seeded key, first regeneration */
   d2d_w_init_genrand(key, s->map_id[e]);
@@ -247,7 +264,6 @@ D2D_WORLDS_QUAL void d2d_worlds_build_seq_env(const d2d_world_spec *s, const d2d
   if (!ok)
     for (int i = 0; i < 3 * P; ++i) pil[i] = 0;
   /* agent records */
-  double *ag = st->agents + (size_t)e * D2D_AF * N;
   for (int k = 0; k < N; ++k) {
     double x, y, vx, vy, r, r2, tr;
     if (k < nr) {
@@ -264,7 +280,8 @@ D2D_WORLDS_QUAL void d2d_worlds_build_seq_env(const d2d_world_spec *s, const d2d
     }
     const int unit = (int)d2d_w_floordiv(r, scale);
     const double rec[D2D_AF] = {x, y, vx, vy, r, r2};
-    for (int f = 0; f < D2D_AF; ++f) ag[f * N + k] = ok ? rec[f] : 0.0;
+    for (int f = 0; f < D2D_AF; ++f)
+      if (!(redraw && (f == D2D_A_VX || f == D2D_A_VY))) ag[f * N + k] = ok ? rec[f] : 0.0;
     st->agent_unit[(size_t)e * N + k] = ok ? unit : 0;
     int32_t *dp = st->dyn_prev + ((size_t)e * N + k) * 3;
     dp[0] = ok ? (int)d2d_w_floordiv(x, scale) : 0;

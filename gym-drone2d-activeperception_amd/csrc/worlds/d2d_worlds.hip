@@ -21,7 +21,8 @@
 //
 // The episode stream (include/d2d_worlds_stream.h) lives here too: worlds_build_masked_kernel is the same body (d2d_worlds_build.inc,
 // shared as text) behind a refill byte, stream_harvest_kernel (one wave per slot) records a finished slot's row, stream_assign_kernel
-// (one workgroup) hands the finished slots their next map ids by a ballot scan, stream_clear_kernel zeroes a refilled slot's rows of a buffer.
+// (one workgroup) hands the finished slots their next map ids by a ballot scan -- consecutive ones, or with include/d2d_worlds_table.h
+// the rows of an episode table --, stream_clear_kernel zeroes a refilled slot's rows of a buffer.
 //
 // Every loop is bounded by d2d_world_spec.max_attempts or by a size of the spec.  Arithmetic is fp64 in the reference's own
 // operation order, compiled with -ffp-contract=off.
@@ -40,6 +41,7 @@
 #define D2D_POW2_TBL_QUAL __device__ const
 #include "d2d_worlds.h"
 #include "../../../include/d2d_worlds_stream.h"
+#include "../../../include/d2d_worlds_table.h"
 
 #define WAVE 64
 
@@ -106,7 +108,7 @@ __device__ __forceinline__ double shfl_f64(double v, int src) {
 }
 
 __global__ __launch_bounds__(WAVE) void worlds_build_kernel(const d2d_world_spec s, const d2d_state st) {
-#include "d2d_worlds_build.inc"   // the body, shared as text with worlds_build_masked_kernel: this kernel compiles to what it always did
+#include "d2d_worlds_build.inc"   // the body, shared as text with worlds_build_masked_kernel
 }
 
 // d2d_worlds_build for the slots of a stream that were just handed a new episode (include/d2d_worlds_stream.h): one wave per slot,
@@ -176,10 +178,20 @@ __global__ __launch_bounds__(WAVE) void stream_harvest_kernel(const d2d_state st
 
 // One workgroup strides over the slots.  The exclusive scan of "harvested" is a ballot inside a wave, the waves' totals through LDS
 // inside a stride, and a carry from stride to stride: no atomics, so the assignment is a function of the flags alone.
+// TABLE: episode k is row k of a table (include/d2d_worlds_table.h) and the slot that receives it copies the row -- its map id, its
+// env_par and its env_tgt -- where the consecutive form writes map_id0 + k; the scan is the same text.
+struct episode_table {
+  const uint32_t *ep_map_id;   // [M]
+  const double *ep_par;        // [M][D2D_WORLDS_ENV_F]
+  const double *ep_tgt;        // [M][T][2]
+  double *env_par, *env_tgt;   // [B][..]: what d2d_worlds_build_masked reads
+  int T;
+};
 #define ASSIGN_BLOCK 1024
+template <bool TABLE>
 __global__ __launch_bounds__(ASSIGN_BLOCK) void stream_assign_kernel(const uint8_t *flags, int B, long long M, uint32_t map_id0,
                                                                     int32_t *slot_episode, uint32_t *map_id, uint8_t *refill,
-                                                                    long long *counts) {
+                                                                    long long *counts, const episode_table tb) {
   __shared__ int wave_total[ASSIGN_BLOCK / WAVE];
   const int tid = threadIdx.x, lane = tid % WAVE, wv = tid / WAVE;
   const long long cursor = counts[0], finished = counts[1];
@@ -202,7 +214,13 @@ __global__ __launch_bounds__(ASSIGN_BLOCK) void stream_assign_kernel(const uint8
         const long long k = cursor + carry + below + before;
         if (k < M) {
           slot_episode[e] = (int32_t)k;
-          map_id[e] = map_id0 + (uint32_t)k;
+          if (TABLE) {
+            map_id[e] = tb.ep_map_id[k];
+            for (int i = 0; i < D2D_WORLDS_ENV_F; ++i) tb.env_par[(size_t)e * D2D_WORLDS_ENV_F + i] = tb.ep_par[(size_t)k * D2D_WORLDS_ENV_F + i];
+            for (int i = 0; i < 2 * tb.T; ++i) tb.env_tgt[(size_t)e * 2 * tb.T + i] = tb.ep_tgt[(size_t)k * 2 * tb.T + i];
+          } else {
+            map_id[e] = map_id0 + (uint32_t)k;
+          }
           refill[e] = 1;
         } else {
           slot_episode[e] = -1;
@@ -324,8 +342,23 @@ int d2d_stream_assign(const uint8_t *flags, int32_t B, int64_t M, uint32_t map_i
   if ((unsigned long long)map_id0 + (unsigned long long)M > 0x100000000ULL) return fail(-1, "d2d_stream_assign: map_id0 + M > 2^32");
   if (B == 0) return 0;
   if (!flags || !slot_episode || !map_id || !refill || !counts) return fail(-1, "d2d_stream_assign: a pointer is NULL");
-  hipLaunchKernelGGL(stream_assign_kernel, dim3(1), dim3(ASSIGN_BLOCK), 0, (hipStream_t)stream, flags, B, (long long)M, map_id0,
-                     slot_episode, map_id, refill, (long long *)counts);
+  hipLaunchKernelGGL(stream_assign_kernel<false>, dim3(1), dim3(ASSIGN_BLOCK), 0, (hipStream_t)stream, flags, B, (long long)M, map_id0,
+                     slot_episode, map_id, refill, (long long *)counts, episode_table{});
+  return launched();
+}
+
+int d2d_stream_assign_table(const uint8_t *flags, int32_t B, int64_t M, int32_t T, const uint32_t *ep_map_id, const double *ep_par,
+                            const double *ep_tgt, int32_t *slot_episode, uint32_t *map_id, double *env_par, double *env_tgt,
+                            uint8_t *refill, int64_t *counts, void *stream) {
+  if (B < 0 || M < 0 || M > D2D_STREAM_MAX_EPISODES || T < 1)
+    return fail(-1, "d2d_stream_assign_table: B >= 0, 0 <= M <= D2D_STREAM_MAX_EPISODES, T >= 1");
+  if (B == 0) return 0;
+  if (!flags || !slot_episode || !map_id || !env_par || !env_tgt || !refill || !counts)
+    return fail(-1, "d2d_stream_assign_table: a pointer is NULL");
+  if (M > 0 && (!ep_map_id || !ep_par || !ep_tgt)) return fail(-1, "d2d_stream_assign_table: a table pointer is NULL");
+  const episode_table tb = {ep_map_id, ep_par, ep_tgt, env_par, env_tgt, (int)T};
+  hipLaunchKernelGGL(stream_assign_kernel<true>, dim3(1), dim3(ASSIGN_BLOCK), 0, (hipStream_t)stream, flags, B, (long long)M, 0u,
+                     slot_episode, map_id, refill, (long long *)counts, tb);
   return launched();
 }
 

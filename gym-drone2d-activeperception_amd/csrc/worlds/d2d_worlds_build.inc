@@ -84,6 +84,28 @@
   }
   if (na < nr) ok = 0;
 
+  // ---- the redraw (D2D_WE_REDRAW): the stream goes on behind the last agent, four words per agent and none depends on another, so
+  // lane j takes agent k0 + j of a pass.  A pass ends at the key's end: what is left of it (fewer than four words) moves into the
+  // carry and the key is regenerated, as for the attempts.  The velocities go straight to the agent records, which the record
+  // loop below then leaves alone: the key is about to make room for numpy's, and no LDS is spent on them.
+  const bool redraw = ok && par[D2D_WE_REDRAW] != 0.0;
+  if (redraw) {
+    double *avx = st.agents + ((size_t)e * D2D_AF + D2D_A_VX) * N, *avy = st.agents + ((size_t)e * D2D_AF + D2D_A_VY) * N;
+    for (int k0 = 0; k0 < N;) {                           // every pass places at least one agent
+      stream_ensure(buf, p, 4, lane);
+      const int n = min(min((D2D_W_BUF - p) / 4, WAVE), N - k0);
+      if (lane < n) {
+        const uint32_t *g = buf + p + 4 * lane;
+        double pvx, pvy;
+        d2d_w_redraw(d2d_rng_temper(g[0]), d2d_rng_temper(g[1]), d2d_rng_temper(g[2]), d2d_rng_temper(g[3]), &pvx, &pvy);
+        avx[k0 + lane] = pvx;
+        avy[k0 + lane] = pvy;
+      }
+      p += 4 * n;
+      k0 += n;
+    }
+  }
+
   // ---- the numpy stream: seeded key, first regeneration
   __syncthreads();
   if (lane == 0) d2d_w_init_genrand(key, seed);
@@ -131,8 +153,10 @@
       u0 = unit + 2;
       ag[D2D_A_PX * N + k] = ok ? x : 0.0;
       ag[D2D_A_PY * N + k] = ok ? y : 0.0;
-      ag[D2D_A_VX * N + k] = ok ? vx : 0.0;
-      ag[D2D_A_VY * N + k] = ok ? vy : 0.0;
+      if (!redraw) {                                      // (a redrawn env is ok, and its lane k wrote both above)
+        ag[D2D_A_VX * N + k] = ok ? vx : 0.0;
+        ag[D2D_A_VY * N + k] = ok ? vy : 0.0;
+      }
       ag[D2D_A_R * N + k] = ok ? r : 0.0;
       ag[D2D_A_R2 * N + k] = ok ? r2 : 0.0;
       st.agent_unit[(size_t)e * N + k] = ok ? unit : 0;

@@ -50,8 +50,21 @@ def _target_xy(t):
     return (float(t[0]), float(t[0])) if t.size == 1 else (float(t[0]), float(t[1]))
 
 
-def init_world(params):
-    """Build one env's initial state.  Returns a dict of numpy arrays (fp64 / int32 / uint8)."""
+def redraw_agent_velocities(world, rnd):
+    """script/validation_speed.py:135-138, the three lines behind `env.reset()`: every agent of `world` (an init_world dict), the
+    static map's cell agents included, gets a preferred velocity of 20 .. 60 px/s in a direction of its own, drawn from `rnd`, the
+    `random` stream as the construction left it.  In place; nothing else of the world depends on the preferred velocities."""
+    agents = world['agents']
+    for k in range(agents.shape[1]):
+        vel = rnd.random() * 40 + 20
+        angle = rnd.random() * 2 * np.pi
+        agents[A.A_VX, k], agents[A.A_VY, k] = vel * np.cos(angle), vel * np.sin(angle)
+    return world
+
+
+def init_world(params, redraw=False):
+    """Build one env's initial state.  Returns a dict of numpy arrays (fp64 / int32 / uint8).  `redraw`: the world of the
+    validation study (redraw_agent_velocities), the preferred velocities redrawn from where the construction left `random`."""
     p = params
     rnd = _random.Random(p.map_id)               # random.seed(map_id)      drone_v2.py:79
     nrs = np.random.RandomState(p.map_id)        # np.random.seed(map_id)   drone_v2.py:80
@@ -161,12 +174,13 @@ def init_world(params):
     assert kind == 'MT19937' and not has_gauss
     rng = np.zeros(A.RNG_WORDS, dtype=np.uint32)
     rng[:624], rng[A.RNG_POS] = key, pos
-    return dict(rng=rng, agents=agents, agent_unit=unit, dyn_prev=dyn_prev, gt=gt,
-                dmap=np.zeros((W, H), dtype=np.uint8),                    # utils.py:722 init_num=0
-                drone=drone, target=np.array([dx, dy], dtype=np.float64),  # traj_planner.py:22
-                targets=tl, counters=counters, group=np.array(group, dtype=np.int64),
-                obstacles=np.array(obstacles, dtype=np.int64).reshape(-1, 3),
-                tracker_radius=tracker_radius, N=N, W=W, H=H, T=T)
+    world = dict(rng=rng, agents=agents, agent_unit=unit, dyn_prev=dyn_prev, gt=gt,
+                 dmap=np.zeros((W, H), dtype=np.uint8),                    # utils.py:722 init_num=0
+                 drone=drone, target=np.array([dx, dy], dtype=np.float64),  # traj_planner.py:22
+                 targets=tl, counters=counters, group=np.array(group, dtype=np.int64),
+                 obstacles=np.array(obstacles, dtype=np.int64).reshape(-1, 3),
+                 tracker_radius=tracker_radius, N=N, W=W, H=H, T=T)
+    return redraw_agent_velocities(world, rnd) if redraw else world
 
 
 def derive_cfg(params, B, N, T=1, planner_mode=A.PLANNER_EXTERNAL, kf_enabled=True, grid_tile=0):

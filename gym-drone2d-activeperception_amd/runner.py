@@ -91,6 +91,14 @@ def record_row(params, map_id, rec):
             int(f[2]), int(f[1]), sm)
 
 
+def study_row(params, rec, agent_speed=None):
+    """record_row for an episode of a table (EpisodeStream(episodes=...), ValidationStudy): `params` is the episode's own Params, so
+    the map id, the start and the target of the row are the episode's.  `agent_speed`: the 'Agent speed' column where it is not
+    agent_max_speed -- script/validation_speed.py:159 writes -1 for its redrawn velocities."""
+    row = record_row(params, params.map_id, rec)
+    return row if agent_speed is None else row[:7] + (agent_speed,) + row[8:]
+
+
 def batch_rows(params, env):
     """One tuple per env of VecDrone2DEnv `env` with the columns of experiment.py:73-103, read off the state as its episodes left it."""
     rec = batch_records(env)
@@ -269,8 +277,16 @@ class EpisodeStream:
     played it nor `refill_every` can change its row, and the rows come out in episode order.  An episode whose world could not be
     placed (column 0 of its record == STREAM_BUILD_FAILED, `build_failed` lists their map ids) has a row of zeros."""
 
-    def __init__(self, params, num_episodes, slots, device='cuda:0', backend=None, jerk_tie=None):
-        from .vec_env import VecDrone2DEnv
+    def __init__(self, params, num_episodes=None, slots=None, device='cuda:0', backend=None, jerk_tie=None, episodes=None,
+                 redraw_agents=False, agent_speed=None):
+        """`episodes`: a table in place of consecutive map ids (VecDrone2DEnv.stream_episodes): a list of Params, or of (map_id,
+        init_position, target_list) triples over `params`; episode k is the world of row k and `rows()` carries the row's map id,
+        start and target.  The env is built from the first rows, so they are the envs as constructed.  `redraw_agents`: every world
+        is that of the validation study, the agents' preferred velocities redrawn behind the construction; `agent_speed`: the rows'
+        'Agent speed' column where it is not agent_max_speed (study_row)."""
+        from .vec_env import VecDrone2DEnv, build_worlds_device_of, table_params
+        if slots is None or (num_episodes is None) == (episodes is None):
+            raise TypeError('EpisodeStream(params, num_episodes, slots) or EpisodeStream(params, episodes=[...], slots=B)')
         p = with_defaults(params)
         stepped = p.planner == 'Jerk_Primitive' or (p.planner == 'Primitive' and p.motion_profile == 'RVO')
         if stepped:
@@ -280,32 +296,141 @@ class EpisodeStream:
             if host_lookahead:
                 raise NotImplementedError('EpisodeStream: LookAhead needs a backend with the device LookAhead / LookGoal stage (a '
                                           'streamed episode has no host policy); ExperimentBatch drives it from the host')
-        self.params, self.num_episodes = p, int(num_episodes)
-        self.env = VecDrone2DEnv(p, int(slots), device=device, backend=backend, planner=p.planner, worlds='device',
-                                 device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie if stepped else None)
+        self.params, self.num_episodes = p, int(num_episodes) if episodes is None else len(episodes)
+        self.episodes, self.agent_speed = None, agent_speed
+        worlds = 'device'
+        if episodes is not None:
+            from ._lib import backend_for
+            backend = backend_for(backend, device)
+            rows = [ep if isinstance(ep, (tuple, list)) else self._accepted_row(ep, p) for ep in episodes]
+            self.episodes = rows
+            # the env's slots are the first rows; surplus slots (fewer episodes than slots) hold the last row's world and are
+            # retired before the first step
+            first = table_params(p, rows[:int(slots)]) if rows else [p]
+            first += [first[-1]] * (int(slots) - len(first))
+            worlds = build_worlds_device_of(first, device, backend, redraw=redraw_agents) if int(slots) else 'device'
+        self.env = VecDrone2DEnv(p, int(slots), device=device, backend=backend, planner=p.planner, worlds=worlds,
+                                 device_plugins=True, gaze=p.gaze_method, jerk_tie=jerk_tie if stepped else None,
+                                 redraw_agents=redraw_agents)
         self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1
         self.steps_run = 0
         self.records = None
+
+    @staticmethod
+    def _accepted_row(ep, p):
+        """a Params row as the runner plays it: the one change the batch runners make to their Params (experiment.py:28-29)"""
+        q = with_defaults(ep)
+        if p.gaze_method == 'NoControl' and q.gaze_method == 'NoControl':
+            q.drone_view_range = 360
+        return q
 
     def run(self, refill_every=64, **kw):
         if self.records is not None:
             raise RuntimeError('EpisodeStream.run(): this stream has run, and its slots hold the last worlds that passed through them; '
                                'rows() returns its rows again, a new EpisodeStream runs the episodes again')
-        self.records = self.env.stream_episodes(self.num_episodes, refill_every, **kw).cpu().numpy()
+        if self.episodes is not None:
+            kw['episodes'] = self.episodes
+        self.records = self.env.stream_episodes(None if self.episodes is not None else self.num_episodes, refill_every, **kw).cpu().numpy()
         self.steps_run = self.env.steps_streamed
         return self.rows()
 
     @property
     def build_failed(self):
         """map ids of the episodes whose world hit max_attempts"""
+        failed = np.nonzero(self.records[:, A.STREAM_R_STEPS] == A.STREAM_BUILD_FAILED)[0]
+        if self.episodes is not None:
+            ps = self.env.episode_params(self.episodes)
+            return [int(ps[int(k)].map_id) for k in failed]
         m0 = self.params.map_id + self.env.env_offset
-        return [m0 + int(k) for k in np.nonzero(self.records[:, A.STREAM_R_STEPS] == A.STREAM_BUILD_FAILED)[0]]
+        return [m0 + int(k) for k in failed]
 
     def rows(self):
         """One tuple per episode, in episode order, with the columns of experiment.py:73-103."""
         if self.records is None:
             raise RuntimeError('EpisodeStream.rows(): run() first')
+        if self.episodes is not None:
+            ps = self.env.episode_params(self.episodes)
+            return [study_row(ps[k], self.records[k], self.agent_speed) for k in range(self.num_episodes)]
         m0 = self.params.map_id + self.env.env_offset
         return [record_row(self.params, m0 + k, self.records[k]) for k in range(self.num_episodes)]
 
     write_csv = _BatchRows.write_csv
+
+
+STUDY_AXIS = (40, 250, 460)          # validation_*.py: axis_range
+
+
+def study_pairs():
+    """The 72 (start, target) pairs of a study cell in the scripts' order: product(product(axis, axis), product(axis, axis)) with
+    start != target (validation_speed.py:118-121)"""
+    from itertools import product
+    return [(s, t) for s, t in product(product(STUDY_AXIS, STUDY_AXIS), product(STUDY_AXIS, STUDY_AXIS)) if s != t]
+
+
+class ValidationStudy:
+    """The reference's validation study -- the runs the difficulty metrics exist for -- with the scripts' loops as data.
+
+    kind 'speed'  script/validation_speed.py: agent_number x agent_radius (5, 10, 15) at the default agent speed, map ids 0 .. 4,
+                  drone_max_speed (20, 40, 60), (planner, gaze) = ('Primitive', 'Oxford'); after env.reset() every agent's preferred
+                  velocity is redrawn (host_init.redraw_agent_velocities, D2D_WE_REDRAW) and the row's 'Agent speed' is the
+                  script's -1.  The script's other pair, ('MPC', 'LookAhead'), is skipped: MPC is out of scope.
+    kind 'size'   script/validation_size.py: agent_number x agent_max_speed (20, 40, 60) at agent_radius = -1, the same maps and
+                  drone speeds, ('Jerk_Primitive', 'NoControl') through Experiment.run: nothing is redrawn there, and the row is
+                  experiment.py's.
+
+    A cell is (agent number, agent size or speed, drone speed, planner, gaze): everything a stream shares.  Its table is 5 maps x
+    72 (start, target) pairs = 360 episodes, maps outermost as in the scripts (which loop the maps outside the drone speeds: the
+    rows are the same, in another order).  `cells()` yields (cell, Params, table of Params); `run()` streams each cell through
+    `slots` resident envs (EpisodeStream(episodes=...)) and returns the reference's CSV rows, or writes them to `path`.
+
+    script/validation_shape.py redraws nothing and needs only a label-grid path per cell, which `static_map` takes
+    (host_init.load_static_map loads any .npy): such a cell is an EpisodeStream(episodes=...) like any other.  Generating its random
+    maps stays with the reference."""
+
+    KINDS = {
+        'speed': dict(second='agent_radius', values=(5, 10, 15), pairs=(('Primitive', 'Oxford'),), redraw=True, agent_speed=-1,
+                      fixed={}),
+        'size': dict(second='agent_max_speed', values=(20, 40, 60), pairs=(('Jerk_Primitive', 'NoControl'),), redraw=False,
+                     agent_speed=None, fixed=dict(agent_radius=-1)),
+    }
+
+    def __init__(self, kind, agent_numbers=(10, 20, 30), drone_max_speeds=(20, 40, 60), map_ids=range(5), **params_kw):
+        if kind not in self.KINDS:
+            raise ValueError(f"ValidationStudy: kind {kind!r}: 'speed' or 'size'")
+        self.kind, self.spec = kind, self.KINDS[kind]
+        self.agent_numbers, self.drone_max_speeds, self.map_ids = tuple(agent_numbers), tuple(drone_max_speeds), tuple(map_ids)
+        self.params_kw = params_kw                      # e.g. max_flight_time, static_map: the same for every cell
+
+    def cells(self):
+        """(cell, Params, episodes) per cell: cell = (agent number, agent size or speed, drone speed, planner, gaze), Params the
+        stream's, episodes the table of len(map_ids) * 72 Params"""
+        import copy
+        from itertools import product
+        from .params import Params
+        sp = self.spec
+        for n, v in product(self.agent_numbers, sp['values']):
+            for d, (planner, gaze) in product(self.drone_max_speeds, sp['pairs']):
+                kw = dict(self.params_kw, agent_number=n, drone_max_speed=d, planner=planner, gaze_method=gaze, debug=False, **sp['fixed'])
+                kw[sp['second']] = v
+                base = Params(**kw)
+                table = []
+                for m in self.map_ids:
+                    for start, target in study_pairs():
+                        p = copy.copy(base)
+                        p.map_id, p.init_position, p.target_list = m, start, [target]
+                        table.append(p)
+                yield (n, v, d, planner, gaze), (table[0] if table else base), table
+
+    def run(self, slots=64, path=None, device='cuda:0', backend=None, refill_every=64, cells=None):
+        """Streams every cell (or those of `cells`, a list of cell tuples) and returns all rows; `path`: also appended there as CSV"""
+        rows = []
+        for cell, p, table in self.cells():
+            if cells is not None and cell not in cells:
+                continue
+            xs = EpisodeStream(p, episodes=table, slots=min(int(slots), len(table)), device=device, backend=backend,
+                               redraw_agents=self.spec['redraw'], agent_speed=self.spec['agent_speed'])
+            got = xs.run(refill_every=refill_every)
+            if path:
+                xs.write_csv(path)
+            rows += got
+        return rows

@@ -44,18 +44,19 @@ from .state import BatchState
 
 
 def _build_world(args):
-    params, map_id = args
+    params, map_id, redraw = args
     p = with_defaults(params)
     p.map_id = map_id
-    return host_init.init_world(p)
+    return host_init.init_world(p, redraw)
 
 
-def build_worlds(params, num_envs, env_offset=0, workers=0):
+def build_worlds(params, num_envs, env_offset=0, workers=0, redraw=False):
     """Host construction of `num_envs` worlds: env i is the reference world for map_id + env_offset + i.
     With `workers` > 0 the (pure Python, GPU-free) construction is spread over forked processes; call
-    this before the process touches the GPU."""
+    this before the process touches the GPU.  `redraw`: the worlds of the validation study, every agent's preferred velocity
+    redrawn behind the construction (host_init.redraw_agent_velocities)."""
     p = with_defaults(params)
-    jobs = [(p, p.map_id + env_offset + i) for i in range(num_envs)]
+    jobs = [(p, p.map_id + env_offset + i, bool(redraw)) for i in range(num_envs)]
     if workers and num_envs >= 64:
         import multiprocessing as mp
         with mp.get_context('fork').Pool(workers) as pool:
@@ -63,10 +64,10 @@ def build_worlds(params, num_envs, env_offset=0, workers=0):
     return [_build_world(j) for j in jobs]
 
 
-def build_worlds_of(params_list, workers=0):
+def build_worlds_of(params_list, workers=0, redraw=False):
     """One world per Params of the list (each with its own map_id and agent settings: the survivability sweep's 540 settings).
-    `workers` as in build_worlds: forked processes, only before the process touches the GPU."""
-    jobs = [(with_defaults(p), p.map_id) for p in params_list]
+    `workers` as in build_worlds: forked processes, only before the process touches the GPU.  `redraw`: as in build_worlds."""
+    jobs = [(with_defaults(p), p.map_id, bool(redraw)) for p in params_list]
     if workers and len(jobs) >= 64:
         import multiprocessing as mp
         with mp.get_context('fork').Pool(workers) as pool:
@@ -74,11 +75,12 @@ def build_worlds_of(params_list, workers=0):
     return [_build_world(j) for j in jobs]
 
 
-def world_inputs(params_list, max_attempts=None, map_ids=None):
+def world_inputs(params_list, max_attempts=None, map_ids=None, redraw=False):
     """What the device construction (include/d2d_worlds.h) needs of `params_list`, one world each, as host arrays: the per-batch
     sizes and tables, the per-env rows, and `group` (the static map's labels, known without building anything).  Everything a
     batch shares (map, agent_number, pillar_number, static map, drone_radius, number of targets) must agree over the list.
-    `map_ids`: the list is ONE Params and world i is that Params with map_ids[i] (a batch of thousands then costs no Python per env)."""
+    `map_ids`: the list is ONE Params and world i is that Params with map_ids[i] (a batch of thousands then costs no Python per env).
+    `redraw`: every env's D2D_WE_REDRAW is set, the worlds of the validation study (host_init.redraw_agent_velocities)."""
     from numpy import cos, pi, sin
     plist = [with_defaults(p) for p in params_list]
     if not plist or (map_ids is not None and len(plist) != 1):
@@ -116,6 +118,7 @@ def world_inputs(params_list, max_attempts=None, map_ids=None):
         a, b = (5, 15) if p.agent_radius == -1 else (p.agent_radius - 2, p.agent_radius + 2)
         env_par[i, [A.WE_R_LO, A.WE_R_W, A.WE_SPEED, A.WE_TRK_R]] = a, b - a, p.agent_max_speed, p.agent_radius
         env_par[i, [A.WE_X0, A.WE_Y0, A.WE_NTGT]] = p.init_position[0], p.init_position[1], len(p.target_list)
+        env_par[i, A.WE_REDRAW] = 1.0 if redraw else 0.0
         for k, t in enumerate(p.target_list):
             env_tgt[i, k] = host_init._target_xy(t)
     if map_ids is not None:
@@ -140,6 +143,23 @@ def world_spec(inp, grid_tile, ptr):
     return s
 
 
+def table_params(params, episodes):
+    """The Params of every row of an episode table (stream_episodes(episodes=...)): a row is a Params, or a (map_id, init_position,
+    target_list) triple over `params`"""
+    import copy
+    out = []
+    for i, ep in enumerate(episodes):
+        if isinstance(ep, (tuple, list)):
+            if len(ep) != 3:
+                raise ValueError(f'stream_episodes(): episode {i}: a row is a Params or a (map_id, init_position, target_list) triple')
+            p = copy.copy(params)
+            p.map_id, p.init_position, p.target_list = ep[0], ep[1], list(ep[2])
+        else:
+            p = with_defaults(ep)
+        out.append(p)
+    return out
+
+
 class DeviceWorlds:
     """Seeded worlds built on the device (HipBackend.build_worlds): `state` holds the `U` distinct ones, `index` ([B] int64 on the
     device, or None) says which of them env i starts from, so a sweep's start cells share one built world.  `tracker_radius` [U, N],
@@ -151,6 +171,7 @@ class DeviceWorlds:
         self.num_envs = self.U if index is None else int(index.numel())
         self.tracker_radius, self.obstacles, self.status = tracker_radius, obstacles, status
         self.group, self.map_ids = inp['group'], inp['map_ids']
+        self.inp = inp                # (an env over these worlds rebuilds a slot of an episode table from it: stream_episodes)
 
     def spread(self, index):
         """The same built worlds under another env -> world index."""
@@ -189,12 +210,13 @@ def _build_into(backend, inp, state, check=True):
 
 
 def build_worlds_device_of(params_list, device='cuda:0', backend=None, grid_layout=None, max_attempts=None, index=None, check=True,
-                           map_ids=None):
+                           map_ids=None, redraw=False):
     """build_worlds_of on the device: one world per Params of the list, built by one launch and left resident (DeviceWorlds).
     `index`: env -> position in the list, for batches that start many envs from one world.  `check=False` returns instead of raising
-    D2DError when an env hit `max_attempts` (DeviceWorlds.status says which; their fields are 0).  `map_ids`: as in world_inputs."""
+    D2DError when an env hit `max_attempts` (DeviceWorlds.status says which; their fields are 0).  `map_ids`, `redraw`: as in
+    world_inputs."""
     backend = backend_for(backend, device)
-    inp = world_inputs(params_list, max_attempts, map_ids)
+    inp = world_inputs(params_list, max_attempts, map_ids, redraw)
     p0 = with_defaults(params_list[0])
     cfg = host_init.derive_cfg(p0, B=inp['U'], N=inp['N'], T=inp['T'], grid_tile=_grid_tile(p0, backend, grid_layout))
     state = BatchState(cfg, torch.device(backend.device))
@@ -203,10 +225,11 @@ def build_worlds_device_of(params_list, device='cuda:0', backend=None, grid_layo
     return DeviceWorlds(state, idx, inp, tr, obs, status)
 
 
-def build_worlds_device(params, num_envs, env_offset=0, device='cuda:0', backend=None, grid_layout=None, max_attempts=None, check=True):
+def build_worlds_device(params, num_envs, env_offset=0, device='cuda:0', backend=None, grid_layout=None, max_attempts=None, check=True,
+                        redraw=False):
     """build_worlds on the device: env i is the reference world for map_id + env_offset + i."""
     return build_worlds_device_of([params], device, backend, grid_layout, max_attempts, check=check,
-                                  map_ids=_seeded(params, num_envs, env_offset))
+                                  map_ids=_seeded(params, num_envs, env_offset), redraw=redraw)
 
 
 def _seeded(params, num_envs, env_offset):
@@ -228,10 +251,15 @@ def _grid_tile(params, backend, grid_layout):
 
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
-                 kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None):
+                 kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None, redraw_agents=False):
         """`jerk_tie`: (tie_perm, tie_eq) for planner='Jerk_Primitive' in place of the table of this host's np.argsort
-        (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it."""
+        (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it.
+        `redraw_agents`: the worlds this env builds itself (worlds=None, worlds='device') are those of the validation study: every
+        agent's preferred velocity redrawn behind the construction (host_init.redraw_agent_velocities, D2D_WE_REDRAW).  The reset
+        snapshot is taken behind the redraw, so reset() and closed_loop(auto_reset=True) restore the redrawn world, as the script's
+        env.reset() and redraw do.  Worlds handed over are taken as they are: build them with `redraw=`."""
         self.params = with_defaults(params)
+        self.redraw_agents = bool(redraw_agents)
         self.num_envs = int(num_envs)
         self.env_offset = int(env_offset)
         planner = planner if planner is not None else self.params.planner
@@ -256,18 +284,21 @@ class VecDrone2DEnv:
             raise ValueError(f"worlds {worlds!r}: a list of host worlds, a DeviceWorlds or 'device'")
         if on_device:
             _needs_device_worlds(backend)
-            inp = None if dw is not None else world_inputs([self.params], map_ids=_seeded(self.params, self.num_envs, self.env_offset))
+            inp = None if dw is not None else world_inputs([self.params], map_ids=_seeded(self.params, self.num_envs, self.env_offset),
+                                                           redraw=self.redraw_agents)
             N, T = (dw.N, dw.T) if dw is not None else (inp['N'], inp['T'])
             if dw is not None and dw.num_envs != self.num_envs:
                 raise ValueError(f'{dw.num_envs} device worlds for {self.num_envs} envs')
         else:
             if worlds is None:
-                worlds = build_worlds(self.params, self.num_envs, self.env_offset, workers=0)
+                worlds = build_worlds(self.params, self.num_envs, self.env_offset, workers=0, redraw=self.redraw_agents)
             N = worlds[0]['N'] if worlds else 0
             T = worlds[0]['T'] if worlds else 1
             if any(w['N'] != N for w in worlds):
                 raise ValueError('all envs of a batch must have the same number of agents')
         self._world_inp = inp if on_device and dw is None else None     # what stream_episodes() rebuilds a slot's world from
+        # ... and what stream_episodes(episodes=...) rebuilds it from where the worlds were handed over, one built world per env
+        self._table_inp = self._world_inp if dw is None else (dw.inp if dw.index is None and hasattr(dw, 'inp') else None)
         self._streamed = False
         self._own_noise = False
         self.cfg = host_init.derive_cfg(self.params, B=self.num_envs, N=N, T=T, planner_mode=self.planner_mode,
@@ -725,7 +756,7 @@ class VecDrone2DEnv:
         return obs, self.reward, done, info
 
     # ------------------------------------------------------------------ a stream of seeded episodes over the resident slots
-    def _needs_stream(self, num_episodes):
+    def _needs_stream(self, num_episodes, episodes=None):
         backend_for(self.backend, None, 'supports_device_worlds', 'has no device world construction, which stream_episodes() rebuilds '
                     'a finished slot with: run the episodes as batches (runner.ExperimentBatch / SteppedExperimentBatch)')
         backend_for(self.backend, None, 'supports_episode_stream', 'has no launches that refill a finished slot '
@@ -733,7 +764,12 @@ class VecDrone2DEnv:
         if self._streamed:
             raise RuntimeError('stream_episodes(): this env has streamed episodes already, so its slots hold the last worlds that '
                                'passed through them, not map ids map_id + 0 ..; build a new VecDrone2DEnv / EpisodeStream for another run')
-        if self._world_inp is None:
+        if episodes is not None:
+            backend_for(self.backend, None, 'supports_episode_table', 'has no assignment from an episode table '
+                        '(include/d2d_worlds_table.h): run the table as batches of host-built worlds (build_worlds_of)')
+            if num_episodes is not None and int(num_episodes) != len(episodes):
+                raise ValueError(f'stream_episodes(): num_episodes {num_episodes} with a table of {len(episodes)} episodes; leave it out')
+        if (self._world_inp if episodes is None else self._table_inp) is None:
             raise NotImplementedError("stream_episodes(): the worlds of this env were built on the host or handed over; a finished slot "
                                       "is rebuilt on the device from its map id, so build the env with worlds='device'")
         if self._own_noise:
@@ -750,18 +786,79 @@ class VecDrone2DEnv:
             self._needs_step_gaze('stream_episodes()')
         if self.jerk is not None and not self._jerk_live(None):
             self._jerk_live(True)              # raises, naming the launch that is missing
-        M = int(num_episodes)
+        M = int(num_episodes) if episodes is None else len(episodes)
         m0 = self.params.map_id + self.env_offset
         if M < 0 or M > A.STREAM_MAX_EPISODES:
             raise ValueError(f'stream_episodes(): {M} episodes: 0 <= num_episodes <= {A.STREAM_MAX_EPISODES}')
-        if m0 + M > 2 ** 32:
+        if episodes is None and m0 + M > 2 ** 32:
             raise ValueError(f'stream_episodes(): map_id {m0} + {M} episodes passes 2**32: numpy seeds with 0 <= map_id < 2**32 only; '
                              'split the run into streams that end below it')
         if self.num_envs and M and bool(self.state.counters[:, A.C_STEPS].ne(0).any() | self.state.flags.ne(0).any()):
             # (one host read before the first step: the first min(B, M) episodes are the envs as constructed)
             raise RuntimeError('stream_episodes(): this env has been stepped, and the first episodes of a stream are the envs as '
                                'constructed; reset() it, or build a new VecDrone2DEnv / EpisodeStream')
-        return M, m0
+        return M, (m0 if episodes is None else self._episode_table(episodes))
+
+    # Params fields a table may vary from row to row: what d2d_worlds_build reads per env (d2d_world_spec.map_id, env_par, env_tgt)
+    TABLE_PER_EPISODE = ('map_id', 'init_position', 'target_list', 'agent_radius', 'agent_max_speed')
+
+    def episode_params(self, episodes):
+        """table_params over the env's own Params"""
+        return table_params(self.params, episodes)
+
+    def _episode_table(self, episodes):
+        """The table of stream_episodes(episodes=...) as the host arrays d2d_stream_assign_table reads (map_id [M] uint32, env_par
+        [M, 8], env_tgt [M, T, 2]), or the ValueError that names the field and the row: a table varies what the world build reads per
+        env -- map_id, init_position, target_list, and the agent radius and speed where the derived d2d_cfg stays equal -- and nothing
+        the batch shares.  The planner and gaze tables read, of the fields a row may vary, agent_radius alone, which the Kalman
+        archive bounds of d2d_cfg pin."""
+        import ctypes
+        p0, B = self.params, self.num_envs
+        plist = self.episode_params(episodes)
+        cfg_fields = [n for n, _ in A.Cfg._fields_]
+        seen = {}
+        for i, p in enumerate(plist):
+            m = p.map_id
+            if not (isinstance(m, (int, np.integer)) and 0 <= int(m) < 2 ** 32):
+                raise ValueError(f'stream_episodes(): episode {i}: map_id {m!r}: numpy seeds with 0 <= map_id < 2**32 only')
+            for name in sorted(set(vars(p0)) | set(vars(p))):
+                if name in self.TABLE_PER_EPISODE:
+                    continue
+                a, b = getattr(p0, name, None), getattr(p, name, None)
+                if (list(a) if isinstance(a, (list, tuple)) else a) != (list(b) if isinstance(b, (list, tuple)) else b):
+                    raise ValueError(f'stream_episodes(): episode {i}: {name} = {b!r}, the stream has {a!r}: {name} is per stream '
+                                     '(the batch shares its map, agent count, planner, gaze, motion profile and tables); a table '
+                                     'varies ' + ', '.join(self.TABLE_PER_EPISODE))
+            if max(len(p.target_list), 1) != self.cfg.T:
+                raise ValueError(f'stream_episodes(): episode {i}: target_list has {len(p.target_list)} targets, the stream has '
+                                 f'{self.cfg.T}: the number of targets is per stream')
+            key = (p.agent_radius, p.agent_max_speed)
+            if key not in seen:
+                c = host_init.derive_cfg(p, B=B, N=self.cfg.N, T=self.cfg.T, planner_mode=self.planner_mode,
+                                         kf_enabled=bool(self.cfg.kf_enabled), grid_tile=self.cfg.grid_tile)
+                seen[key] = next((n for n in cfg_fields if n not in ('noise_rows', 'noise_row0') and getattr(c, n) != getattr(self.cfg, n)),
+                                 None)
+            if seen[key] is not None:
+                n = seen[key]
+                raise ValueError(f'stream_episodes(): episode {i}: agent_radius = {p.agent_radius!r} (the stream has {p0.agent_radius!r}) '
+                                 f'moves d2d_cfg.{n}: the derived cfg is per stream')
+            if float(p.agent_radius) != float(p0.agent_radius):
+                raise ValueError(f'stream_episodes(): episode {i}: agent_radius = {p.agent_radius!r} (the stream has {p0.agent_radius!r}): '
+                                 'the planner and gaze tables hold it, and they are per stream')
+        if not plist:
+            T = self.cfg.T
+            return dict(map_id=np.zeros(0, np.uint32), env_par=np.zeros((0, A.WORLDS_ENV_F)), env_tgt=np.zeros((0, T, 2)), map_ids=[])
+        tab = world_inputs(plist, redraw=self.redraw_agents)
+        inp = self._table_inp
+        if tab['N'] != self.cfg.N or tab['P'] != inp['P']:
+            raise ValueError('stream_episodes(): episode 0: the table\'s static map gives another agent count than the env has')
+        for i in range(min(B, len(plist))):
+            for name in ('map_id', 'env_par', 'env_tgt'):
+                if not np.array_equal(tab[name][i], inp[name][i]):
+                    raise ValueError(f'stream_episodes(): episode {i}: {name} {tab[name][i].tolist()} is not that of env {i} as '
+                                     f'constructed ({inp[name][i].tolist()}): the first min(num_envs, episodes) rows are the envs as '
+                                     'constructed (runner.EpisodeStream(params, episodes=...) builds them so)')
+        return {k: tab[k] for k in ('map_id', 'env_par', 'env_tgt', 'map_ids')}
 
     def _episode_steps(self, n):
         """`n` steps of the env's own episode loop, finished envs left alone: closed_loop(freeze_done=True) where closed_loop() runs,
@@ -803,7 +900,7 @@ class VecDrone2DEnv:
                 self.jerk.t[name].masked_fill_(m, 0)
         self.reset_plugins(refill)
 
-    def stream_episodes(self, num_episodes, refill_every=64, max_attempts=None, trace=None):
+    def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
         """Episodes map_id + 0 .. map_id + num_episodes - 1 over the env's `num_envs` slots: a slot whose episode has ended is
         handed the next map id, its world is rebuilt in place on the device and everything that hangs on it is put back, so the
         slots stay full while the queue lasts and memory is bounded by the slots, not the episodes.  Returns the records
@@ -818,27 +915,40 @@ class VecDrone2DEnv:
 
         A world that cannot be placed within `max_attempts` (default: the constructor's) ends at once with column 0 of its record
         == STREAM_BUILD_FAILED.  `trace`: a list that receives (steps so far, slots live) per refill, for measurement (one more
-        host read each).  The env has then played other worlds than its snapshot: reset() refuses afterwards."""
-        for _ in self.stream_rounds(num_episodes, refill_every, max_attempts, trace):
+        host read each).  The env has then played other worlds than its snapshot: reset() refuses afterwards.
+
+        `episodes`: a table in place of consecutive map ids -- a list of Params, or of (map_id, init_position, target_list) triples
+        over the env's own Params; episode k is the world of row k (include/d2d_worlds_table.h: the slot that receives it copies the
+        row's map id, env_par and env_tgt, and the same masked build reads them).  This is a cell of the reference's validation
+        study: 5 maps x 72 (start, target) pairs (runner.ValidationStudy).  A row varies map_id, init_position and target_list
+        freely, and the agent radius and speed only where the derived d2d_cfg stays equal (the Kalman archive bounds take
+        agent_radius); everything else is per stream, and a row that differs is refused with a ValueError that names the field and
+        the row.  The first min(num_envs, len(episodes)) rows must be the envs as constructed, which runner.EpisodeStream(params,
+        episodes=...) sees to.  With `redraw_agents` every row's world is redrawn."""
+        for _ in self.stream_rounds(num_episodes, refill_every, max_attempts, trace, episodes):
             pass
         return self.stream_rows
 
-    def stream_rounds(self, num_episodes, refill_every=64, max_attempts=None, trace=None):
+    def stream_rounds(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
         """stream_episodes() as a generator that hands control back after every refill that rebuilt a slot: yields (episodes finished,
         the refill bytes [B] uint8 of the round); the records so far are `stream_rows`.  For callers that look at the slots in
         between (the tests do)."""
-        M, m0 = self._needs_stream(num_episodes)
+        M, m0 = self._needs_stream(num_episodes, episodes)        # m0: the first map id, or the table's arrays
+        table = None if episodes is None else m0
         B, dev, s = self.num_envs, self.device, self.state
         every = max(1, int(refill_every))
         self.stream_rows = rows = torch.full((M, A.STREAM_ROW_F), -1, dtype=torch.int32, device=dev)
         self.steps_streamed = 0
         if M == 0 or B == 0:
             return
-        inp = dict(self._world_inp)
+        inp = dict(self._world_inp if table is None else self._table_inp)
         if max_attempts is not None:
             inp['max_attempts'] = int(max_attempts)
         up = {n: torch.from_numpy(inp[n]).to(dev) for n in ('unit', 'cells', 'env_par', 'env_tgt')}
         up['map_id'] = torch.from_numpy(inp['map_id'].view(np.int32).copy()).to(dev)
+        if table is not None:                  # the rows a slot copies when it is handed an episode (the launches only read them)
+            ep = (torch.from_numpy(table['map_id'].view(np.int32).copy()).to(dev), torch.from_numpy(table['env_par']).to(dev),
+                  torch.from_numpy(table['env_tgt']).to(dev))
         up['status'] = torch.zeros(B, dtype=torch.int32, device=dev)
         N, P = self.cfg.N, inp['P']
         radius0 = self.plugins.trk_radius0 if self.plugins is not None else self.jerk.trk_radius0     # [B, max(N, 1)]: the output's shape for N > 0
@@ -852,7 +962,7 @@ class VecDrone2DEnv:
             slot_episode[M:] = -1
             s.flags[M:, A.F_DONE] = 1
         self._streamed = True
-        self._stream_keep = (up, slot_episode, refill, counts)            # (the launches are asynchronous: the arrays outlive them)
+        self._stream_keep = (up, slot_episode, refill, counts, table and ep)   # (the launches are asynchronous: the arrays outlive them)
         finished, guard = 0, (-(-M // B) + 1) * (int(np.ceil(self.params.max_flight_time / self.params.dt)) + 1 + every)
         while finished < M:
             if self.steps_streamed > guard:
@@ -860,7 +970,11 @@ class VecDrone2DEnv:
             self._episode_steps(every)
             self.steps_streamed += every
             self.backend.stream_harvest(self.cfg, self._st, slot_episode, rows)
-            self.backend.stream_assign(s.flags, M, m0, slot_episode, up['map_id'], refill, counts)
+            if table is None:
+                self.backend.stream_assign(s.flags, M, m0, slot_episode, up['map_id'], refill, counts)
+            else:
+                self.backend.stream_assign_table(s.flags, ep[0], ep[1], ep[2], slot_episode, up['map_id'], up['env_par'], up['env_tgt'],
+                                                 refill, counts)
             now = int(counts[1])               # the only host read
             if trace is not None:
                 trace.append((self.steps_streamed, int((s.flags[:, A.F_DONE] == 0).sum()) + int(refill.sum())))

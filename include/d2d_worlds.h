@@ -34,6 +34,11 @@ extern "C" {
 #define D2D_WE_X0 4        /* init_position                                                                   */
 #define D2D_WE_Y0 5
 #define D2D_WE_NTGT 6      /* len(target_list) <= T                                                           */
+#define D2D_WE_REDRAW 7    /* 0: the world as constructed.  Non-zero: the world of script/validation_speed.py:134-138 -- after the
+                              last agent is placed the env's Python `random` stream goes on, and every agent in agent order, the
+                              static map's cell agents included, gets the preferred velocity (agents[A_VX], agents[A_VY])
+                              vel * (cos, sin)(angle) with vel = random() * 40 + 20, angle = random() * 2 * pi.  Nothing else of
+                              the env changes: the numpy stream (d2d_state.rng) is not touched                  */
 
 #define D2D_WORLDS_MAX_ATTEMPTS 65536 /* default of d2d_world_spec.max_attempts */
 
