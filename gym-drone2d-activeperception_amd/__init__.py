@@ -8,6 +8,7 @@ Layout
   host_init.py   world construction = the reference's __init__ (seeded, bit-identical)
   state.py       device-resident batch state
   vec_env.py     VecDrone2DEnv: B envs stepped in lock-step on one GPU
+  action_stream.py  ActionStream: seeded episodes over resident slots, stepped with the caller's gaze actions (VecDrone2DEnv.action_stream)
   env.py         Drone2DEnv2: single-env gym facade (gym-2d-perception-v2) over VecDrone2DEnv
   planners.py    --planner plugin surface (traj_planner.py): Primitive / NoMove = views of the device stages
   gaze.py        --gaze_method plugin surface (yaw_planner.py): Oxford = the device stage, NoControl, Rotating
@@ -24,3 +25,11 @@ __version__ = '0.1.0'
 
 from . import _abi            # noqa: F401
 from .params import Params, with_defaults   # noqa: F401
+
+
+def __getattr__(name):
+    # ActionStream lives in a module that imports torch: loaded on first use, so that `import drone2d_amd` stays light
+    if name == 'ActionStream':
+        from .action_stream import ActionStream
+        return ActionStream
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

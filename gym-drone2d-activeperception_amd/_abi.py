@@ -185,6 +185,30 @@ def bind_worlds_table(lib):
     return _bind(lib, 'd2d_', sig, TABLE_ENTRY_POINTS)
 
 
+# include/d2d_worlds_turn.h: the turn of a stream the caller steps itself (VecDrone2DEnv.action_stream)
+RESTORE_MAX_ITEMS, RESTORE_PARTS = 32, 8
+RESTORE_ZERO, RESTORE_COPY = 0, 1
+TURN_ENTRY_POINTS = ('stream_restore', 'stream_explored')
+
+
+class RestoreItem(C.Structure):
+    """include/d2d_worlds_turn.h `d2d_restore_item`."""
+    _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p)] + \
+               [(n, C.c_int64) for n in ('dst_stride', 'src_stride', 'dst_off', 'src_off', 'bytes')] + \
+               [('kind', C.c_int32), ('reserved', C.c_int32)]
+
+
+def bind_worlds_turn(lib):
+    """argtypes / restypes of include/d2d_worlds_turn.h on the loaded libd2d_worlds.so: additions to that library, looked up as
+    optional symbols (a build without them binds nothing here, and its version is the same)."""
+    P, V, I = C.POINTER, C.c_void_p, C.c_int32
+    sig = {
+        'stream_restore': (C.c_int, [V, I, V, I, V]),
+        'stream_explored': (C.c_int, [P(State), I, I, I, I, V, V]),
+    }
+    return _bind(lib, 'd2d_', sig, TURN_ENTRY_POINTS)
+
+
 # ---- include/d2d_metrics.h: the difficulty metrics on the device (csrc/metrics/libd2d_metrics.so, its own version) ----
 D2D_METRICS_VERSION = 2
 VO_MAX_B, VO_MAX_P, VO_MAX_ELEMS = 65535, 64 * 65535, 0x7fffffff

@@ -126,6 +126,7 @@ class HipBackend:
         self.wlib, self.wfn = load_worlds_library()
         self.sfn = A.bind_worlds_stream(self.wlib)                        # include/d2d_worlds_stream.h, where the build has it
         self.sfn.update(A.bind_worlds_table(self.wlib))                   # include/d2d_worlds_table.h, likewise
+        self.sfn.update(A.bind_worlds_turn(self.wlib))                    # include/d2d_worlds_turn.h, likewise
         self.mlib = self.mfn = None       # libd2d_metrics.so: loaded by the first metric call, so that a tree without it runs the rest
         self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
         self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
@@ -220,7 +221,8 @@ class HipBackend:
 
     def _stream_fn(self, name, *args):
         if name not in self.sfn:
-            header = 'd2d_worlds_table.h' if name in A.TABLE_ENTRY_POINTS else 'd2d_worlds_stream.h'
+            header = ('d2d_worlds_table.h' if name in A.TABLE_ENTRY_POINTS else
+                      'd2d_worlds_turn.h' if name in A.TURN_ENTRY_POINTS else 'd2d_worlds_stream.h')
             raise D2DError(f'{WORLDS_LIB_PATH} has no d2d_{name} (include/{header}): rebuild it with csrc/worlds/build.sh')
         _check(self.sfn[name](*args, self._stream()), self.wfn, 'd2d_worlds')
 
@@ -250,6 +252,21 @@ class HipBackend:
         """d2d_stream_clear: rows e of the per-slot tensor t [B, ...] with refill [B] uint8 set become 0, nothing else is written"""
         if t.numel():
             self._stream_fn('stream_clear', t.data_ptr(), t[0].numel() * t.element_size(), refill.data_ptr(), t.shape[0])
+
+    @property
+    def supports_action_stream(self):
+        """include/d2d_worlds_turn.h: the restore and the per-step count of a stream the caller steps itself (action_stream).
+        Optional symbols of libd2d_worlds.so: true where the built library has both"""
+        return all(n in self.sfn for n in A.TURN_ENTRY_POINTS)
+
+    def stream_restore(self, items, n_items, refill):
+        """d2d_stream_restore: `items` is a device tensor that holds n_items packed _abi.RestoreItem records
+        (action_stream.pack_items); every item is applied to the slots with refill [B] uint8 set, nothing else is written"""
+        self._stream_fn('stream_restore', items.data_ptr(), int(n_items), refill.data_ptr(), refill.shape[0])
+
+    def stream_explored(self, cfg, st, cells):
+        """d2d_stream_explored: cells [B] int32 = the non-zero cells of every slot's dmap, as stream_harvest counts them"""
+        self._stream_fn('stream_explored', C.byref(st), cells.shape[0], cfg.W, cfg.H, cfg.grid_tile, cells.data_ptr())
 
     def _metrics(self, name, *args):
         if self.mfn is None:

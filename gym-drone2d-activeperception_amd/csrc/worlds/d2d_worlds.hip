@@ -22,7 +22,10 @@
 // The episode stream (include/d2d_worlds_stream.h) lives here too: worlds_build_masked_kernel is the same body (d2d_worlds_build.inc,
 // shared as text) behind a refill byte, stream_harvest_kernel (one wave per slot) records a finished slot's row, stream_assign_kernel
 // (one workgroup) hands the finished slots their next map ids by a ballot scan -- consecutive ones, or with include/d2d_worlds_table.h
-// the rows of an episode table --, stream_clear_kernel zeroes a refilled slot's rows of a buffer.
+// the rows of an episode table --, stream_clear_kernel zeroes a refilled slot's rows of a buffer.  The turn of a stream the caller
+// steps itself (include/d2d_worlds_turn.h) is the tail of this file, d2d_worlds_turn.inc: stream_restore_kernel puts back a refilled
+// slot's ranges outside the world in one launch, stream_explored_kernel counts every slot's discovered cells with the harvest's own
+// text (d2d_stream_count.inc).
 //
 // Every loop is bounded by d2d_world_spec.max_attempts or by a size of the spec.  Arithmetic is fp64 in the reference's own
 // operation order, compiled with -ffp-contract=off.
@@ -42,6 +45,7 @@
 #include "d2d_worlds.h"
 #include "../../../include/d2d_worlds_stream.h"
 #include "../../../include/d2d_worlds_table.h"
+#include "d2d_restore.h"
 
 #define WAVE 64
 
@@ -144,28 +148,7 @@ __global__ __launch_bounds__(WAVE) void stream_harvest_kernel(const d2d_state st
   if (!st.flags[(size_t)e * 4 + D2D_STREAM_F_DONE]) return;
   const int ep = slot_episode[e];
   if (ep < 0 || (long long)ep >= M) return;
-  const int G = d2d_w_grid_bytes(W, H, tile);
-  const uint8_t *p = st.dmap + (size_t)e * G;
-  int cnt = 0;
-  if (!tile) {
-    int head = (int)((4u - (unsigned)((uintptr_t)p & 3u)) & 3u);
-    if (head > G) head = G;
-    if (lane < head) cnt += p[lane] != 0;
-    const int nw = (G - head) >> 2;
-    const uint32_t *w = (const uint32_t *)(p + head);
-    for (int q = lane; q < nw; q += WAVE) cnt += nonzero_bytes(w[q], 4);
-    const int t0 = head + 4 * nw;
-    if (t0 + lane < G) cnt += p[t0 + lane] != 0;
-  } else {
-    const uint32_t *w = (const uint32_t *)p;        // e * G is a multiple of 256 and the field's base is a word's
-    for (int q = lane; q < (G >> 2); q += WAVE) {
-      int i, j;
-      d2d_w_cell_of(4 * q, W, H, tile, &i, &j);     // the word's first cell; the other three follow it in j
-      const int n = i < W ? min(max(H - j, 0), 4) : 0;
-      if (n) cnt += nonzero_bytes(w[q], n);
-    }
-  }
-  cnt = wave_sum(cnt);
+#include "d2d_stream_count.inc"   // cnt: the non-zero cells of the slot's dmap, shared as text with stream_explored_kernel
   if (lane < D2D_STREAM_ROW_F) {
     const int32_t *c = st.counters + (size_t)e * D2D_CF;
     const uint8_t *f = st.flags + (size_t)e * 4;
@@ -373,3 +356,5 @@ int d2d_stream_clear(void *base, int64_t bytes_per_slot, const uint8_t *refill, 
 }
 
 }  // extern "C"
+
+#include "d2d_worlds_turn.inc"   // d2d_stream_restore, d2d_stream_explored (include/d2d_worlds_turn.h)

@@ -756,7 +756,9 @@ class VecDrone2DEnv:
         return obs, self.reward, done, info
 
     # ------------------------------------------------------------------ a stream of seeded episodes over the resident slots
-    def _needs_stream(self, num_episodes, episodes=None):
+    def _needs_stream(self, num_episodes, episodes=None, external=False):
+        """The refusals of stream_episodes(), in its order; `external`: of action_stream(), which differs in the gaze clause alone (the
+        caller's actions in place of a policy the device evaluates) and keeps every other text"""
         backend_for(self.backend, None, 'supports_device_worlds', 'has no device world construction, which stream_episodes() rebuilds '
                     'a finished slot with: run the episodes as batches (runner.ExperimentBatch / SteppedExperimentBatch)')
         backend_for(self.backend, None, 'supports_episode_stream', 'has no launches that refill a finished slot '
@@ -779,10 +781,21 @@ class VecDrone2DEnv:
         if self.cfg.sigma != 0.0 and not self.device_noise:
             raise NotImplementedError('stream_episodes(): var_cam != 0 needs a backend that draws the measurement noise on the device '
                                       '(supports_device_noise); run the episodes as batches with set_noise()')
-        if self.device_gaze is None or (self.plugins is None and self.jerk is None):
+        if external:
+            if self.device_gaze is not None or not ((self.plugins is not None and self.plugins.planner == A.PLAN_PRIMITIVE) or self.jerk is not None):
+                raise RuntimeError("action_stream() needs device_plugins=True, planner='Primitive' or 'Jerk_Primitive' and gaze='external' "
+                                   '(the caller supplies the action of every step); stream_episodes() plays the episodes of a gaze '
+                                   'policy the device evaluates')
+            backend_for(self.backend, None, 'supports_action_stream', 'has no restore and count launches for a stream the caller steps '
+                        '(include/d2d_worlds_turn.h): step the env yourself with step() and reset(mask)')
+            if self.plugins is not None and self.rvo:
+                for flag, header in (('supports_stepped_plugins', 'd2d_stepped.h'), ('supports_rvo_live', 'd2d_rvo_live.h')):
+                    backend_for(self.backend, None, flag, f'has no launches that leave finished envs alone (include/{header}): '
+                                'action_stream() with the Primitive plugins under RVO runs on the HIP backend')
+        elif self.device_gaze is None or (self.plugins is None and self.jerk is None):
             raise RuntimeError('stream_episodes() needs device_plugins=True and a gaze policy the device evaluates '
                                "(not gaze='external'); step the env yourself for anything else")
-        if self.plugins is not None and self.rvo:
+        elif self.plugins is not None and self.rvo:
             self._needs_step_gaze('stream_episodes()')
         if self.jerk is not None and not self._jerk_live(None):
             self._jerk_live(True)              # raises, naming the launch that is missing
@@ -929,23 +942,17 @@ class VecDrone2DEnv:
             pass
         return self.stream_rows
 
-    def stream_rounds(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
-        """stream_episodes() as a generator that hands control back after every refill that rebuilt a slot: yields (episodes finished,
-        the refill bytes [B] uint8 of the round); the records so far are `stream_rows`.  For callers that look at the slots in
-        between (the tests do)."""
-        M, m0 = self._needs_stream(num_episodes, episodes)        # m0: the first map id, or the table's arrays
-        table = None if episodes is None else m0
+    def _stream_arrays(self, M, table, max_attempts=None):
+        """What a stream of M > 0 episodes over the B > 0 slots keeps on the device (stream_rounds, action_stream.ActionStream): the
+        spec's arrays `up`, the table's rows `ep` (or None), the d2d_world_spec of the masked build, slot_episode, the refill bytes and
+        counts = (cursor, finished).  Retires the surplus slots and marks the env as streamed"""
         B, dev, s = self.num_envs, self.device, self.state
-        every = max(1, int(refill_every))
-        self.stream_rows = rows = torch.full((M, A.STREAM_ROW_F), -1, dtype=torch.int32, device=dev)
-        self.steps_streamed = 0
-        if M == 0 or B == 0:
-            return
         inp = dict(self._world_inp if table is None else self._table_inp)
         if max_attempts is not None:
             inp['max_attempts'] = int(max_attempts)
         up = {n: torch.from_numpy(inp[n]).to(dev) for n in ('unit', 'cells', 'env_par', 'env_tgt')}
         up['map_id'] = torch.from_numpy(inp['map_id'].view(np.int32).copy()).to(dev)
+        ep = None
         if table is not None:                  # the rows a slot copies when it is handed an episode (the launches only read them)
             ep = (torch.from_numpy(table['map_id'].view(np.int32).copy()).to(dev), torch.from_numpy(table['env_par']).to(dev),
                   torch.from_numpy(table['env_tgt']).to(dev))
@@ -962,7 +969,22 @@ class VecDrone2DEnv:
             slot_episode[M:] = -1
             s.flags[M:, A.F_DONE] = 1
         self._streamed = True
-        self._stream_keep = (up, slot_episode, refill, counts, table and ep)   # (the launches are asynchronous: the arrays outlive them)
+        self._stream_keep = (up, slot_episode, refill, counts, ep)   # (the launches are asynchronous: the arrays outlive them)
+        return up, ep, spec, slot_episode, refill, counts
+
+    def stream_rounds(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
+        """stream_episodes() as a generator that hands control back after every refill that rebuilt a slot: yields (episodes finished,
+        the refill bytes [B] uint8 of the round); the records so far are `stream_rows`.  For callers that look at the slots in
+        between (the tests do)."""
+        M, m0 = self._needs_stream(num_episodes, episodes)        # m0: the first map id, or the table's arrays
+        table = None if episodes is None else m0
+        B, dev, s = self.num_envs, self.device, self.state
+        every = max(1, int(refill_every))
+        self.stream_rows = rows = torch.full((M, A.STREAM_ROW_F), -1, dtype=torch.int32, device=dev)
+        self.steps_streamed = 0
+        if M == 0 or B == 0:
+            return
+        up, ep, spec, slot_episode, refill, counts = self._stream_arrays(M, table, max_attempts)
         finished, guard = 0, (-(-M // B) + 1) * (int(np.ceil(self.params.max_flight_time / self.params.dt)) + 1 + every)
         while finished < M:
             if self.steps_streamed > guard:
@@ -987,6 +1009,24 @@ class VecDrone2DEnv:
             self._refill_rest(refill)
             yield finished, refill
         self.sync()
+
+    def action_stream(self, num_episodes=None, refill_every=4, max_attempts=None, episodes=None):
+        """A stream of seeded episodes over the env's slots that the caller steps with its own gaze actions (action_stream.ActionStream):
+        `stream.step(actions)` takes [B] float64 on the device and returns (obs, terms, done, info), and a slot whose episode has ended
+        is in the next seeded world at the caller's next step -- harvest, assignment, masked build, d2d_stream_restore
+        (include/d2d_worlds_turn.h) and the masked resets are queued at the start of every `refill_every`-th call, and nothing is read
+        back.  For an env built with device_plugins=True, planner='Primitive' or 'Jerk_Primitive', gaze='external' and
+        worlds='device', under either motion profile; every other refusal is stream_episodes()'s, in its words.
+
+        Episodes, `max_attempts` and `episodes` (a table) are stream_episodes()'s.  `num_episodes=None` without a table: as many as
+        the records can number, STREAM_MAX_EPISODES clipped to the map ids below 2**32 -- `rows` is allocated for all of them
+        (32 bytes an episode), so a learner that knows its budget passes it."""
+        from .action_stream import ActionStream
+        m0 = self.params.map_id + self.env_offset
+        if num_episodes is None and episodes is None:
+            num_episodes = max(0, min(A.STREAM_MAX_EPISODES, 2 ** 32 - m0))
+        M, first = self._needs_stream(num_episodes, episodes, external=True)
+        return ActionStream(self, M, first, None if episodes is None else first, refill_every, max_attempts)
 
     def closed_loop(self, nsteps=1, auto_reset=False, freeze_done=False):
         """`nsteps` reference-style steps with the plugins on the device: a = Oxford.plan(info); perceive;
