@@ -1789,7 +1789,7 @@ __device__ __forceinline__ void store_regs(const d2d_state &s, int e, const EnvR
 template <bool FULL, bool WIDE, bool CONE, bool TILED = false>
 __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, int e, int lane, uint32_t stages,
                                         const Geom &g, const LdsView &L, double action, EnvRegs &r, size_t noise_off = 0,
-                                        bool load_r = false, const StepIn *given = nullptr) {
+                                        bool load_r = false, const StepIn *given = nullptr, bool late_obs = false) {
   using RayMask = std::conditional_t<WIDE, unsigned long long, unsigned int>;
   const int N = c.N, W = c.W, H = c.H;
   const double inv_scale = 1.0 / c.scale;
@@ -2044,6 +2044,18 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
     wave_sync_lds();
     if constexpr (FULL) obs_full(c, s, e, lane, L, ncx_d, ncy_d, r);
     else st_obs(c, s, e, lane, L, r);
+  } else if (late_obs && __builtin_amdgcn_readfirstlane(r.done)) {
+    // a hidden step of the persistent loop (k_closed: no observation stage in the mask, nothing staged for it) whose collision stage
+    // ended the episode: the observation is the env's result (D2D_DONE_FREEZE), so it is cut now -- from the explored map as this
+    // step's rays left it in global memory, which holds every byte they patched into the LDS copy of a visible step.  Its own
+    // round trip: once per episode under RESET and FREEZE, on every step of an env that stays done under CONTINUE (include/d2d.h).
+    wave_sync_global();
+    if constexpr (FULL) grid_stage(dm, L.dmt, W * H, lane);
+    else tile_load<9>(gx, ct, (unsigned char *)L.dmt, dm, W, H, lane, (unsigned char)0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wave_sync_lds();
+    if constexpr (FULL) obs_full(c, s, e, lane, L, ncx_d, ncy_d, r);
+    else st_obs(c, s, e, lane, L, r);
   }
   D2D_STAMP(12);
 }
@@ -2246,10 +2258,11 @@ struct ClosedArgs {
   d2d_plan p;
   d2d_state init;
   int on_done, nsteps;
+  int obs_every;  // D2D_OBS_EVERY_STEP=1: every step writes the observation (hidden_stages below)
 };
 static_assert(sizeof(ClosedArgs) <= D2D_LAUNCH_ARGS_BYTES, "d2d_plan.launch_args (D2D_LAUNCH_ARGS_BYTES) is too small for the parked launch arguments");
 
-__global__ void k_closed_args(ClosedArgs *dst, d2d_cfg c, d2d_state s, d2d_plan p, d2d_state init, int on_done, int nsteps) {
+__global__ void k_closed_args(ClosedArgs *dst, d2d_cfg c, d2d_state s, d2d_plan p, d2d_state init, int on_done, int nsteps, int obs_every) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     dst->c = c;
     dst->s = s;
@@ -2257,6 +2270,7 @@ __global__ void k_closed_args(ClosedArgs *dst, d2d_cfg c, d2d_state s, d2d_plan 
     dst->init = init;
     dst->on_done = on_done;
     dst->nsteps = nsteps;
+    dst->obs_every = obs_every;
   }
 }
 
@@ -2367,13 +2381,22 @@ __device__ __forceinline__ void ph_plan_search(const ClosedArgs *ap, int e_, int
   wave_sync_global();
 }
 
+// Hidden steps.  Nothing on the device reads obs_local / obs_yaw, and the host sees them only after the launch: a step of the
+// persistent loop writes them only if it is the launch's last or its collision stage ended the episode (include/d2d.h,
+// d2d_closed_loop).  Every other step runs the phase's HIDDEN instantiation: the same stages without D2D_ST_OBS -- no staging of the
+// explored map, no crop tile, no crop -- and the observation cut behind the collision stage if that set `done` (run_env, late_obs).
+// A compile-time variant picked by a wave-uniform branch in the step loop, not a branch around the loads: the act phase's prologue
+// stays one batch.
+__host__ __device__ constexpr uint32_t hidden_stages(uint32_t stages) { return stages & ~(uint32_t)D2D_ST_OBS; }
+__host__ __device__ constexpr bool late_obs_of(uint32_t stages) { return (stages & D2D_ST_COLLIDE) && !(stages & D2D_ST_OBS); }
+
 // The planner's every-step part AND the act phase in one call, for the steps whose trajectory is kept (96 % of them): the
 // planner's result reaches the control stage in registers -- no store -> fence -> load between the two, one call, one scalar-load
 // round trip for the arguments, one fence fewer per step.  Returns -1 when Primitive.plan has to search (the caller runs
 // ph_plan_search and then ph_stages<ACT>), else the episode flag the collision stage wrote.
 // `walls_ok`: the env's "every remaining waypoint passed the wall test and only rays have written the map since" flag
 // (plan_env_quick), carried by the caller across the steps of a launch.
-template <int SPEC, bool PDEF>
+template <int SPEC, bool PDEF, uint32_t ACT = D2D_ST_ACT>
 __device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds_off_, int &walls_ok) {
   const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
@@ -2406,7 +2429,7 @@ __device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds
   const Geom g = make_geom(c, wpb, spec_ncap(SPEC), spec_full(SPEC));
   const LdsView L = carve(base, g, c.L);
   EnvRegs r;
-  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, D2D_ST_ACT, g, L, a->s.action[e], r, 0, true, &in);
+  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, ACT, g, L, a->s.action[e], r, 0, true, &in, late_obs_of(ACT));
   if (lane == 0) store_regs(a->s, e, r);
   wave_sync_global();
   return r.done;
@@ -2445,7 +2468,7 @@ __device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int 
   const size_t noise_off = c.noise_rows > 1 ? (size_t)((c.noise_row0 + tstep) % c.noise_rows) * c.B * c.N * 2 : 0;
   // (the plain order of loads, not run_env's one-batch form: with the agents' first pass held in registers across the grid copies
   // this phase saves 13 callee-saved registers per call instead of 6 -- 1.8 KB of scratch writes per env-step for +0.6 %)
-  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, noise_off, false);
+  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, noise_off, false, nullptr, late_obs_of(STAGES));
   if (lane == 0) store_regs(a->s, e, r);
   wave_sync_global();
 #ifdef D2D_CHAIN_PROF
@@ -2466,7 +2489,7 @@ __device__ __forceinline__ int ph_stages(const ClosedArgs *ap, int e_, int lds_o
   const Geom g = make_geom(c, wpb, spec_ncap(SPEC), spec_full(SPEC));
   const LdsView L = carve(base, g, c.L);
   EnvRegs r;
-  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, 0, true);
+  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, 0, true, nullptr, late_obs_of(STAGES));
   if (lane == 0) store_regs(a->s, e, r);
   wave_sync_global();
   return r.done;
@@ -2494,6 +2517,7 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
   }
   const int nsteps = a->nsteps;
   const bool freeze = a->on_done == D2D_DONE_FREEZE;
+  const bool obs_every = a->obs_every != 0;
   int nsearch = 0;
   int walls_ok = 0;  // (plan_env_quick: nothing is known about the trajectory's waypoints at the start of a launch)
 #ifdef D2D_CHAIN_PROF
@@ -2507,6 +2531,7 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
 #pragma unroll 1
   for (int t = 0; t < nsteps; ++t) {
     if (freeze && flag_done != 0) break;  // one episode per env: it stays as it ended
+    const bool visible = obs_every || t == nsteps - 1;  // (hidden_stages; wave-uniform: scalar operands only)
     if (split) {
       // An env that searches often is the one the launch ends up waiting for (the worlds repeat, so it stays that env):
       // past one search per 32 steps of this launch all its phases issue first on their SIMD.  Its chain is
@@ -2518,7 +2543,8 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
       const unsigned long long q0 = __builtin_amdgcn_s_memtime();
 #endif
       // the planner's every-step part and, unless it has to search, the act phase behind it in the same call (ph_plan_act)
-      const int pa = __builtin_amdgcn_readfirstlane(ph_plan_act<SPEC, PDEF>(a, e, off, walls_ok));
+      const int pa = __builtin_amdgcn_readfirstlane(visible ? ph_plan_act<SPEC, PDEF, D2D_ST_ACT>(a, e, off, walls_ok)
+                                                            : ph_plan_act<SPEC, PDEF, hidden_stages(D2D_ST_ACT)>(a, e, off, walls_ok));
 #ifdef D2D_CHAIN_PROF
       D2D_PHASE_ADD(2, q0);  // (planner every-step part + act of the steps without a search)
 #endif
@@ -2534,7 +2560,8 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
         D2D_PHASE_ADD(3, s0);
         const unsigned long long a0 = __builtin_amdgcn_s_memtime();
 #endif
-        flag_done = __builtin_amdgcn_readfirstlane(ph_stages<SPEC, D2D_ST_ACT>(a, e, off));
+        flag_done = __builtin_amdgcn_readfirstlane(visible ? ph_stages<SPEC, D2D_ST_ACT>(a, e, off)
+                                                           : ph_stages<SPEC, hidden_stages(D2D_ST_ACT)>(a, e, off));
 #ifdef D2D_CHAIN_PROF
         D2D_PHASE_ADD(4, a0);  // (act of the steps with a search)
 #endif
@@ -2542,7 +2569,8 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
         flag_done = pa;
       }
     } else {
-      flag_done = __builtin_amdgcn_readfirstlane(ph_gaze_stages<SPEC, PDEF, D2D_ST_ALL>(a, e, off, t, flag_done));
+      flag_done = __builtin_amdgcn_readfirstlane(visible ? ph_gaze_stages<SPEC, PDEF, D2D_ST_ALL>(a, e, off, t, flag_done)
+                                                         : ph_gaze_stages<SPEC, PDEF, hidden_stages(D2D_ST_ALL)>(a, e, off, t, flag_done));
     }
   }
 #ifdef D2D_CHAIN_PROF
@@ -2949,8 +2977,12 @@ int d2d_closed_loop(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p, int
     const Launch l = pick_launch(*c, p);
     if (l.wpb >= 1) {
       ClosedArgs *dev = (ClosedArgs *)p->launch_args;
+      // D2D_OBS_EVERY_STEP=1 in the environment, read at every call: every step of the launch writes the observation, as every step
+      // did before the hidden variant (same-process A/B, tests/test_gpu_hidden_obs.py); the arrays after the launch are the same
+      const char *obs_env = getenv("D2D_OBS_EVERY_STEP");
+      const bool obs_every = obs_env && obs_env[0] == '1' && obs_env[1] == '\0';
       hipLaunchKernelGGL(k_closed_args, dim3(1), dim3(64), 0, (hipStream_t)stream, dev, *c, *s, *p, auto_reset ? *init : *s,
-                         (int)on_done, (int)nsteps);
+                         (int)on_done, (int)nsteps, obs_every ? 1 : 0);
       auto launch = [&](auto kernel) {
         lds_optin(kernel, l.lds());
         hipLaunchKernelGGL(kernel, env_grid(c->B, l.wpb), env_block(l.wpb), l.lds(), (hipStream_t)stream, (const ClosedArgs *)dev);

@@ -425,7 +425,17 @@ int d2d_plan_stage(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan
  * caller sees the terminal state after the call) is put back to the snapshot `init` with fresh plugin state at the
  * start of its next step, the way the reference's sweeps start the next episode (main.py:26-57); with FREEZE a
  * finished env is left exactly as its last step left it (Experiment.run stops at done, experiment.py:68-72).
- * `init` may be NULL unless on_done == D2D_DONE_RESET. */
+ * `init` may be NULL unless on_done == D2D_DONE_RESET.
+ * Observation visibility.  The persistent launch writes an env's observation (obs_local and obs_yaw, together or not at all) only
+ * on a step the host can see: the last step of the call, and every step whose collision stage set the env's `done` flag (under
+ * every `on_done`: once per episode under RESET and FREEZE -- under D2D_DONE_FREEZE that observation is the env's result; under
+ * D2D_DONE_CONTINUE an env that stays done, having reached its last goal, dead-locked or run past max_steps, sets the flag again
+ * on every following step and so writes its observation on each of them, by a round trip of its own that costs such an env more
+ * than the observation stage did).  Every other step of the call is a hidden step: it runs without the observation stage, and
+ * nothing on the device reads the observation.  After the call every env therefore holds exactly the bytes it would hold had every
+ * step written them.  D2D_OBS_EVERY_STEP=1 in the environment, read at every call, makes every step write the observation
+ * (same-process A/B).  The per-stage path (plan->launch_args == NULL), d2d_rollout, d2d_run_stages and d2d_step write it on every
+ * step. */
 int d2d_closed_loop(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan, int32_t nsteps,
                     int32_t on_done, const d2d_state *init, void *stream);
 
