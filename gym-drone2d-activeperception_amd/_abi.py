@@ -121,6 +121,28 @@ ENTRY_POINTS = ('abi_version', 'last_error', 'step', 'perceive', 'act', 'run_sta
                 'tan_array', 'gaze_stage', 'plan_stage', 'closed_loop', 'plan_reset', 'sincos_array', 'launch_shape')
 
 
+# ---- include/d2d_swept.h: the swept-trajectory map of the Primitive planner as an observation (additions to libd2d_hip.so) ----
+SWEPT_ENTRY_POINTS = ('swept_mark', 'swept_crop')
+SWEPT_FIELDS = ('map', 'obs', 'count', 'live')
+SWEPT_MAX_SIDE = 256
+
+
+class Swept(C.Structure):
+    """include/d2d_swept.h `d2d_swept`."""
+    _fields_ = [(n, C.c_void_p) for n in SWEPT_FIELDS]
+
+
+def bind_swept(lib, prefix='d2d_'):
+    """argtypes / restypes of include/d2d_swept.h on the loaded libd2d_hip.so: additions to that library, looked up as optional
+    symbols (a build without them binds nothing here, and its ABI version is the same)."""
+    P, V = C.POINTER, C.c_void_p
+    sig = {
+        'swept_mark': (C.c_int, [P(Cfg), P(State), P(Plan), P(Swept), V]),
+        'swept_crop': (C.c_int, [P(Cfg), P(State), P(Swept), V]),
+    }
+    return _bind(lib, prefix, sig, SWEPT_ENTRY_POINTS)
+
+
 # ---- include/d2d_worlds.h: the world construction on the device (csrc/worlds/libd2d_worlds.so, its own version) ----
 D2D_WORLDS_VERSION = 1
 WORLDS_ENV_F = 8

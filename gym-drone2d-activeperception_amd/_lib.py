@@ -123,6 +123,7 @@ class HipBackend:
         self.torch = torch
         self.device = torch.device(device)
         self.lib, self.fn = load_library()
+        self.wpfn = A.bind_swept(self.lib)                                # include/d2d_swept.h, where the build has it
         self.wlib, self.wfn = load_worlds_library()
         self.sfn = A.bind_worlds_stream(self.wlib)                        # include/d2d_worlds_stream.h, where the build has it
         self.sfn.update(A.bind_worlds_table(self.wlib))                   # include/d2d_worlds_table.h, likewise
@@ -178,6 +179,25 @@ class HipBackend:
     def plan_stage_live(self, cfg, st, plan):
         """d2d_plan_stage_live: d2d_plan_stage for the envs that are not done"""
         self._chk(self._stepped('plan_stage_live')(C.byref(cfg), C.byref(st), C.byref(plan), self._stream()))
+
+    @property
+    def supports_swept_obs(self):
+        """include/d2d_swept.h: the swept-trajectory map and its crop (VecDrone2DEnv(..., swept_obs=True)).  Optional symbols of
+        libd2d_hip.so: true where the built library has both"""
+        return all(n in self.wpfn for n in A.SWEPT_ENTRY_POINTS)
+
+    def _swept(self, name):
+        if name not in self.wpfn:
+            raise D2DError(f'{LIB_PATH} has no d2d_{name} (include/d2d_swept.h): rebuild it with csrc/build.sh')
+        return self.wpfn[name]
+
+    def swept_mark(self, cfg, st, plan, sw):
+        """d2d_swept_mark: the map replan_check is about to return, for the envs that are not done (between perceive and plan)"""
+        self._chk(self._swept('swept_mark')(C.byref(cfg), C.byref(st), C.byref(plan), C.byref(sw), self._stream()))
+
+    def swept_crop(self, cfg, st, sw):
+        """d2d_swept_crop: the crop of that map around the drone's cell, for the envs the last mark ran for (after act)"""
+        self._chk(self._swept('swept_crop')(C.byref(cfg), C.byref(st), C.byref(sw), self._stream()))
 
     def closed_loop(self, cfg, st, plan, nsteps, on_done=0, init=None):
         self._chk(self.fn['closed_loop'](C.byref(cfg), C.byref(st), C.byref(plan), nsteps, int(on_done),

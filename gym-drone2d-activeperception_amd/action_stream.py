@@ -37,7 +37,8 @@ def restore_items(env, prev_cells=None):
     VecDrone2DEnv._refill_rest touches outside the masked resets -- the per-step outputs, the action, under RVO the velocities as
     state.init_rvo leaves them (zero for the k = min(agent_number, N) seeded agents, the preferred velocity out of the `agents`
     planes for the static map's cell agents), the plan statistics and the storage no reset covers (trajectory, boxes, search nodes
-    and hash, the scratch half of the velocity swap), the Jerk_Primitive choice and status -- and `prev_cells`, the previous count
+    and hash, the scratch half of the velocity swap), the Jerk_Primitive choice and status, with swept_obs the swept map, its
+    crop and its count (include/d2d_swept.h) -- and `prev_cells`, the previous count
     of terms['explored'].  A buffer of no elements is left out."""
     s, items = env.state, []
 
@@ -66,6 +67,9 @@ def restore_items(env, prev_cells=None):
     if env.jerk is not None:
         for name in ('choice', 'stat'):
             zero('jerk.' + name, env.jerk.t[name])
+    if getattr(env, 'swept', None) is not None and len(env.swept) > 1:      # a rebuilt slot has a zero swept map at its step 0
+        for name in ('map', 'obs', 'count'):
+            zero('swept.' + name, env.swept[name])
     if prev_cells is not None:
         zero('explored_prev', prev_cells)
     return items

@@ -47,6 +47,7 @@
 #include "../../include/d2d.h"
 #include "../../include/d2d_hooks.h"
 #include "../../include/d2d_stepped.h"
+#include "../../include/d2d_swept.h"
 
 #define D2D_TAN_QUAL __device__ __forceinline__
 #define D2D_TAN_TBL_QUAL __device__ const
@@ -2582,6 +2583,10 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
 #endif
 }
 
+// include/d2d_swept.h: the swept-trajectory map and its crop (behind every other kernel: the code object of the kernels above stays
+// as it was)
+#include "d2d_swept.h"
+
 // ------------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ------------------------------------------------------------------------------------------------
@@ -2955,6 +2960,10 @@ int d2d_plan_stage_live(const d2d_cfg *c, const d2d_state *s, const d2d_plan *p,
   if (rc) return rc;
   return plan_launch(c, s, p, true, stream);
 }
+
+// include/d2d_swept.h: d2d_swept_mark and d2d_swept_crop, the entry points of the stage (the second half of csrc/d2d_swept.h)
+#define D2D_SWEPT_ENTRY_POINTS
+#include "d2d_swept.h"
 
 int d2d_plan_reset(const d2d_cfg *c, const d2d_plan *p, const uint8_t *mask, int32_t mask_stride, void *stream) {
   if (!c || !p) return fail(-1, "null cfg/plan");

@@ -251,13 +251,18 @@ def _grid_tile(params, backend, grid_layout):
 
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
-                 kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None, redraw_agents=False):
+                 kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None, redraw_agents=False,
+                 swept_obs=False):
         """`jerk_tie`: (tie_perm, tie_eq) for planner='Jerk_Primitive' in place of the table of this host's np.argsort
         (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it.
         `redraw_agents`: the worlds this env builds itself (worlds=None, worlds='device') are those of the validation study: every
         agent's preferred velocity redrawn behind the construction (host_init.redraw_agent_velocities, D2D_WE_REDRAW).  The reset
         snapshot is taken behind the redraw, so reset() and closed_loop(auto_reset=True) restore the redrawn world, as the script's
-        env.reset() and redraw do.  Worlds handed over are taken as they are: build them with `redraw=`."""
+        env.reset() and redraw do.  Worlds handed over are taken as they are: build them with `redraw=`.
+        `swept_obs`: obs['swep_map'] is the crop of the map Primitive.replan_check returned in the step (the cells the stored
+        trajectory will pass through and when: envs/training_v3.py:141, :206-213, include/d2d_swept.h) instead of the explored map a
+        second time (envs/drone_v2.py:252-253); `swept_map` and `swept_count` hold the full map and the waypoints marked.  The env then
+        steps through policy_step() / run_episodes() / action_stream() and stream_episodes(), one launch per stage."""
         self.params = with_defaults(params)
         self.redraw_agents = bool(redraw_agents)
         self.num_envs = int(num_envs)
@@ -402,6 +407,64 @@ class VecDrone2DEnv:
             if planner == 'Primitive' and gaze not in ('external', None):
                 self.step_gaze = gaze
             self.device_gaze = gaze if gaze not in ('external', None) else None
+        self.swept_obs = bool(swept_obs)
+        self.swept = None                  # the buffers of include/d2d_swept.h (Jerk_Primitive: the crop alone, zero for ever)
+        if self.swept_obs:
+            self._init_swept(planner)
+
+    def _init_swept(self, planner):
+        """The refusals and the buffers of swept_obs=True"""
+        if self.plugins is None and self.jerk is None:
+            raise RuntimeError('swept_obs=True needs device_plugins=True: the swept map is what the device planner\'s replan_check '
+                               "returns (planner='Primitive' or 'Jerk_Primitive')")
+        if self.jerk is None and self.plugins.planner != A.PLAN_PRIMITIVE:
+            raise NotImplementedError(f"swept_obs=True: planner {planner!r} has no swept map of its own -- NoMove.replan_check returns "
+                                      "the explored map itself (traj_planner.py:75-76), which obs['local_map'] already crops; the "
+                                      "device computes it for planner='Primitive' (and zeros for 'Jerk_Primitive')")
+        backend_for(self.backend, None, 'supports_swept_obs', 'has no swept-map launches (include/d2d_swept.h: d2d_swept_mark, '
+                    'd2d_swept_crop): swept_obs=True runs on a HIP library built with them')
+        if self.cfg.W > A.SWEPT_MAX_SIDE or self.cfg.H > A.SWEPT_MAX_SIDE:
+            raise NotImplementedError(f'swept_obs=True: a map of {self.cfg.W} x {self.cfg.H} cells; the stage holds an env\'s map in LDS '
+                                      f'whole and takes at most {A.SWEPT_MAX_SIDE} x {A.SWEPT_MAX_SIDE} (the channel would cost '
+                                      f'{self.cfg.W * self.cfg.H} bytes per env and step)')
+        B, L, dev = self.num_envs, self.cfg.L, self.device
+        self.swept = {'obs': torch.zeros((B, L, L), dtype=torch.uint8, device=dev)}
+        if self.jerk is not None:          # an empty trajectory at every replan_check (plan() appends one waypoint, step_pos pops it)
+            return
+        self.swept.update(map=torch.zeros_like(self.state.dmap), count=torch.zeros(B, dtype=torch.int32, device=dev),
+                          live=torch.zeros(B, dtype=torch.uint8, device=dev))
+        self._swept = A.Swept()
+        for n in A.SWEPT_FIELDS:
+            t = self.swept[n]
+            setattr(self._swept, n, t.data_ptr() if t.numel() else self.state._dummy.data_ptr())
+
+    @property
+    def swept_map(self):
+        """[B, W, H] uint8: the map replan_check returned in each env's last live step (None under Jerk_Primitive: all zero)"""
+        if not self.swept_obs:
+            raise RuntimeError('swept_map: build the env with swept_obs=True')
+        m = self.swept.get('map')
+        if m is not None and self.cfg.grid_tile:
+            from .state import untile_grid
+            return untile_grid(m, self.cfg.W, self.cfg.H, self.cfg.grid_tile)
+        return m
+
+    @property
+    def swept_count(self):
+        """[B] int32: the waypoints marked in that map (first tracker hit + 1, or the trajectory's length)"""
+        if not self.swept_obs:
+            raise RuntimeError('swept_count: build the env with swept_obs=True')
+        return self.swept.get('count')
+
+    def _swept_zero(self, mask=None):
+        """map, crop and count of a fresh world (envs/training_v3.py:219-224), for all envs or those of `mask`"""
+        if self.swept is None or len(self.swept) == 1:
+            return
+        for t in self.swept.values():
+            if mask is None:
+                t.zero_()
+            elif t.numel():
+                t.masked_fill_(mask.bool().view((-1,) + (1,) * (t.dim() - 1)), 0)
 
     # ------------------------------------------------------------------ gym-like surface (batched)
     @property
@@ -420,6 +483,7 @@ class VecDrone2DEnv:
             vel, vel0 = self.state.agent_vel, self.init_state.agent_vel
             vel.copy_(vel0 if mask is None else torch.where(mask.bool()[:, None, None], vel0, vel))
         self.reset_plugins(mask)
+        self._swept_zero(mask)
         return {}
 
     def _rvo_agents(self):
@@ -486,13 +550,16 @@ class VecDrone2DEnv:
                         f"{' under RVO' if self.rvo else ''} runs on the HIP backend")
         return not lacks
 
-    def _plugins_step(self):
+    def _plugins_step(self, before_plan=None):
         """One step of the episode loop with the Primitive plugins, finished envs left alone by every launch: d2d_gaze_stage_live
         (nothing for the resident constants), under RVO the two _live RVO launches, d2d_run_stages(PERCEIVE | SKIP_DONE) with this
         step's row of the noise, d2d_plan_stage_live, d2d_run_stages(ACT | SKIP_DONE).  The gaze decision reads the drone, the
         trajectory, seen_step and the trackers, none of which the RVO launches write, so the order is the reference's: policy.plan,
-        then step() with the agents first"""
+        then step() with the agents first.  With swept_obs d2d_swept_mark goes between the perceive and the plan launch (the
+        trajectory as replan_check is about to find it) and d2d_swept_crop behind the act launch (include/d2d_swept.h);
+        `before_plan()`, a hook for tests, is called behind the mark with everything it read still in place"""
         noise = self.state.noise if self.cfg.noise_rows > 1 else None
+        swept = self.swept is not None
         try:
             if self._plan.gaze != A.GAZE_NONE:
                 self.backend.gaze_stage_live(self.cfg, self._st, self._plan)
@@ -501,8 +568,14 @@ class VecDrone2DEnv:
             if self.rvo:
                 self._rvo_agents_live()
             self.backend.run_stages(self.cfg, self._st, (A.ST_PERCEIVE & ~A.ST_AGENTS if self.rvo else A.ST_PERCEIVE) | A.ST_SKIP_DONE)
+            if swept:
+                self.backend.swept_mark(self.cfg, self._st, self._plan, self._swept)
+            if before_plan is not None:
+                before_plan()
             self.backend.plan_stage_live(self.cfg, self._st, self._plan)
             self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
+            if swept:
+                self.backend.swept_crop(self.cfg, self._st, self._swept)
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -748,6 +821,8 @@ class VecDrone2DEnv:
         s = self.state
         obs = {'local_map': s.obs_local.unsqueeze(1), 'swep_map': s.obs_local.unsqueeze(1),   # drone_v2.py:251-255
                'yaw_angle': s.obs_yaw.unsqueeze(1)}
+        if self.swept is not None:             # training_v3.py:206-213: the crop of what replan_check returned
+            obs['swep_map'] = self.swept['obs'].unsqueeze(1)
         done = s.flags[:, A.F_DONE].bool()
         info = {'collision_flag': s.flags[:, A.F_COLLISION], 'dead_lock_flag': s.flags[:, A.F_DEADLOCK],
                 'freezing_flag': s.flags[:, A.F_FREEZING], 'state_machine': s.counters[:, A.C_SM],
@@ -797,6 +872,9 @@ class VecDrone2DEnv:
                                "(not gaze='external'); step the env yourself for anything else")
         elif self.plugins is not None and self.rvo:
             self._needs_step_gaze('stream_episodes()')
+        if self.plugins is not None and self.swept is not None:    # the per-stage path under CVM too (_episode_steps)
+            backend_for(self.backend, None, 'supports_stepped_plugins', 'has no gaze and plan stages that leave finished envs alone '
+                        '(include/d2d_stepped.h): a stream with swept_obs=True runs one launch per stage')
         if self.jerk is not None and not self._jerk_live(None):
             self._jerk_live(True)              # raises, naming the launch that is missing
         M = int(num_episodes) if episodes is None else len(episodes)
@@ -875,8 +953,8 @@ class VecDrone2DEnv:
 
     def _episode_steps(self, n):
         """`n` steps of the env's own episode loop, finished envs left alone: closed_loop(freeze_done=True) where closed_loop() runs,
-        the step sequences of run_episodes() elsewhere"""
-        if self.plugins is not None and not self.rvo:
+        the step sequences of run_episodes() elsewhere -- and with swept_obs, whose map exists only between two stages of a step"""
+        if self.plugins is not None and not self.rvo and self.swept is None:
             self.closed_loop(n, freeze_done=True)
         elif self.plugins is not None:
             for _ in range(n):
@@ -911,6 +989,7 @@ class VecDrone2DEnv:
         if self.jerk is not None:
             for name in ('choice', 'stat'):
                 self.jerk.t[name].masked_fill_(m, 0)
+        self._swept_zero(refill)
         self.reset_plugins(refill)
 
     def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
@@ -1045,6 +1124,11 @@ class VecDrone2DEnv:
                                       'lives in libd2d_rvo.so); step the env with step() / perceive() + act(), or run episodes '
                                       'through runner.Experiment.  run_episodes() / runner.SteppedExperimentBatch play whole '
                                       'episodes under this profile as a batch')
+        if self.swept is not None:
+            raise NotImplementedError('closed_loop(): swept_obs=True does not run inside the persistent closed loop (the swept map '
+                                      'exists only between the perceive and the plan stage of a step, and the launches of '
+                                      'include/d2d_swept.h go between them); step the env with action_stream() / policy_step() / '
+                                      'run_episodes(), which run one launch per stage')
         if auto_reset and self._streamed:
             raise RuntimeError('closed_loop(auto_reset=True): this env has streamed episodes (stream_episodes), so its slots hold other '
                                'worlds than the snapshot an auto reset restores; build a new VecDrone2DEnv for the map ids you want')
