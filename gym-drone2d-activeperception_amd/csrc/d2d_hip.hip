@@ -658,8 +658,11 @@ __device__ __forceinline__ void st_agents(const d2d_cfg &c, const d2d_state &s, 
 }
 
 // The agents stage as one loop, loads and stores together: a launch of k_stages (run_env without `load_r`).
+// `dyn_feed` false (wave-uniform: the persistent loop's steps without the dynamic-grid stage, run_env's dyn_skip): what only that stage
+// reads -- the agent's unit, its previous block (dyn_prev), the cell of its new one -- is neither loaded nor staged.
 __device__ __forceinline__ void st_agents_plain(const d2d_cfg &c, const d2d_state &s, int e, int lane, const Geom &g,
-                                          const LdsView &L, double inv_scale, bool move, bool want_trk, bool light = false) {
+                                          const LdsView &L, double inv_scale, bool move, bool want_trk, bool light = false,
+                                          bool dyn_feed = true) {
   const int N = c.N;
   double *__restrict__ ag = s.agents + (size_t)e * D2D_AF * N;
   const int *__restrict__ prev = s.dyn_prev + (size_t)e * N * 3;
@@ -680,8 +683,13 @@ __device__ __forceinline__ void st_agents_plain(const d2d_cfg &c, const d2d_stat
       continue;
     }
     const double r2 = ag[D2D_A_R2 * N + k];
-    const int u = s.agent_unit[(size_t)e * N + k];
-    const int p0 = prev[3 * k], p1 = prev[3 * k + 1], p2 = prev[3 * k + 2];
+    int u = 0, p0 = 0, p1 = 0, p2 = 0;
+    if (dyn_feed) {
+      u = s.agent_unit[(size_t)e * N + k];
+      p0 = prev[3 * k];
+      p1 = prev[3 * k + 1];
+      p2 = prev[3 * k + 2];
+    }
     int klen = 1;
     if (want_trk && c.kf_enabled) klen = s.kf_len[(size_t)e * N + k];
     if (move) {
@@ -715,12 +723,14 @@ __device__ __forceinline__ void st_agents_plain(const d2d_cfg &c, const d2d_stat
     L.ay[k] = py;
     L.ar[k] = rr;
     L.ar2[k] = r2;
-    L.ncx[k] = cell_fast(px, c.scale, inv_scale);
-    L.ncy[k] = cell_fast(py, c.scale, inv_scale);
-    L.nu[k] = u;
-    L.pcx[k] = p0;
-    L.pcy[k] = p1;
-    L.pu[k] = p2;
+    if (dyn_feed) {
+      L.ncx[k] = cell_fast(px, c.scale, inv_scale);
+      L.ncy[k] = cell_fast(py, c.scale, inv_scale);
+      L.nu[k] = u;
+      L.pcx[k] = p0;
+      L.pcy[k] = p1;
+      L.pu[k] = p2;
+    }
     L.act[k] = act;
     L.klen[k] = klen;
   }
@@ -1274,6 +1284,37 @@ __device__ __forceinline__ void dyn_full(const d2d_cfg &c, const d2d_state &s, i
   }
 }
 
+// The gate of the deferred dynamic-grid update (include/d2d.h, d2d_closed_loop; ph_gaze_stages below): may this env's stage be
+// left out of the steps nobody sees?  Skipping is exact iff (a) every cell of its ground truth holds OCCUPIED, UNOCCUPIED or DYNAMIC
+// and (b) every DYNAMIC cell lies inside a block of dyn_prev.  Tested on the LDS copy of the ground truth where dyn_full would run
+// (the rays are done with it): every agent ORs a mark (bit 7) into its PREVIOUS block, then one pass over the copy's dwords looks
+// for a byte outside {1, 2, 0x81, 0x82, 0x83} and takes the marks out again -- dyn_full may follow on the same copy.  Wave-uniform
+// result.  W * H is a multiple of 4 here (Geom.full).
+__device__ __forceinline__ bool dyn_gate_full(const d2d_cfg &c, int lane, const LdsView &L) {
+  const int N = c.N, W = c.W, H = c.H;
+  unsigned char *g8 = (unsigned char *)L.gtw;
+  for (int k = lane; k < N; k += WAVE) {
+    const int pcx = L.pcx[k], pcy = L.pcy[k], pu = L.pu[k];
+    const int i1 = min(pcx + pu + 1, W), j1 = min(pcy + pu + 1, H);
+    for (int i = max(pcx - pu, 0); i < i1; ++i)
+      for (int j = max(pcy - pu, 0); j < j1; ++j) g8[i * H + j] = g8[i * H + j] | 0x80;
+  }
+  wave_sync_lds();
+  bool bad = false;
+  const int nd = (W * H) >> 2;
+  for (int i = lane; i < nd; i += WAVE) {
+    const unsigned int w = L.gtw[i];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const unsigned int v = (w >> (8 * b)) & 0xffu;
+      bad = bad || !(((v & 0x7fu) - 1u < 2u) || v == (0x80u | D2D_DYNAMIC));
+    }
+    if (w & 0x80808080u) L.gtw[i] = w & 0x7f7f7f7fu;
+  }
+  wave_sync_lds();
+  return !__any(bad);
+}
+
 // utils.py:780-784 + envs/drone_v2.py:251-255 from the LDS copy of the whole explored map (which the rays patched): the
 // L x L crop around cell (ci, cj), zero outside the map.  Two crop rows per pass (lanes 0-31 / 32-63 = the first 32 columns of
 // rows 2t / 2t + 1), further columns by lane = row: indices advance by constants, no division.
@@ -1790,11 +1831,16 @@ __device__ __forceinline__ void store_regs(const d2d_state &s, int e, const EnvR
 template <bool FULL, bool WIDE, bool CONE, bool TILED = false>
 __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, int e, int lane, uint32_t stages,
                                         const Geom &g, const LdsView &L, double action, EnvRegs &r, size_t noise_off = 0,
-                                        bool load_r = false, const StepIn *given = nullptr, bool late_obs = false) {
+                                        bool load_r = false, const StepIn *given = nullptr, bool late_obs = false,
+                                        int *dyn_gate = nullptr, bool dyn_visible = true, bool dyn_skip = false) {
+  // `dyn_gate` (the persistent loop's whole-grid kernels; else null: the stage runs whenever the mask holds it): the env's state of the
+  // deferred dynamic-grid update, wave-uniform -- 0: not tested yet (dyn_gate_full runs here), 1: the stage may be left out of steps
+  // that are not `dyn_visible`, 2: it runs on every step.  `dyn_skip` (wave-uniform; state 1 on a step that is not dyn-visible): the stage
+  // and what only it reads are left out of this step.
   using RayMask = std::conditional_t<WIDE, unsigned long long, unsigned int>;
   const int N = c.N, W = c.W, H = c.H;
   const double inv_scale = 1.0 / c.scale;
-  const bool do_ray = stages & D2D_ST_RAYCAST, do_dyn = stages & D2D_ST_DYNGRID, do_trk = stages & D2D_ST_TRACKER;
+  const bool do_ray = stages & D2D_ST_RAYCAST, do_dyn = (stages & D2D_ST_DYNGRID) && !dyn_skip, do_trk = stages & D2D_ST_TRACKER;
   const bool do_col = stages & D2D_ST_COLLIDE, do_obs = stages & D2D_ST_OBS, do_ctl = stages & D2D_ST_CONTROL;
   const GridIx<TILED> gx = {H, (H + 15) >> 4};
   const size_t gbytes = TILED ? (size_t)((W + 15) >> 4) * (size_t)((H + 15) >> 4) * 256 : (size_t)W * H;
@@ -1854,7 +1900,7 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
       if (lane < N) agent_apply(c, s, e, lane, L, inv_scale, move, agents_light, ag0);
       if (N > WAVE) st_agents(c, s, e, lane, g, L, inv_scale, move, do_trk || do_col, agents_light, WAVE);
     } else {
-      st_agents_plain(c, s, e, lane, g, L, inv_scale, move, do_trk || do_col, agents_light);
+      st_agents_plain(c, s, e, lane, g, L, inv_scale, move, do_trk || do_col, agents_light, do_dyn || !dyn_gate);
     }
     if (do_trk && !do_ray)  // hit mask of an earlier launch: stage it where the raycast leaves it
       for (int k = lane; k < N; k += WAVE) L.hit[k] = s.hit[(size_t)e * N + k];
@@ -2012,7 +2058,14 @@ __device__ __forceinline__ void run_env(const d2d_cfg &c, const d2d_state &s, in
   D2D_STAMP(8);
   if (do_dyn) {
     if constexpr (FULL) {
-      dyn_full(c, s, e, lane, L, gt);
+      bool run = true;
+      if (dyn_gate) {
+        int gs = __builtin_amdgcn_readfirstlane(*dyn_gate);
+        if (gs == 0) gs = dyn_gate_full(c, lane, L) ? 1 : 2;
+        *dyn_gate = gs;
+        run = dyn_visible || gs == 2;
+      }
+      if (run) dyn_full(c, s, e, lane, L, gt);
     } else if (g.dyn2p) {  // grids above 256 x 256 cells: clear, fence, fetch again and mark (dyn_apply)
       if (lane < N) dyn_apply<1>(gx, c, s, e, lane, g, L, gt, dc);
       for (int k = WAVE + lane; k < N; k += WAVE) {
@@ -2391,6 +2444,19 @@ __device__ __forceinline__ void ph_plan_search(const ClosedArgs *ap, int e_, int
 __host__ __device__ constexpr uint32_t hidden_stages(uint32_t stages) { return stages & ~(uint32_t)D2D_ST_OBS; }
 __host__ __device__ constexpr bool late_obs_of(uint32_t stages) { return (stages & D2D_ST_COLLIDE) && !(stages & D2D_ST_OBS); }
 
+// Hidden steps, second rule: no dynamic-grid stage.  Nothing on the device reads what the stage writes -- rays and collision probes
+// test the ground truth for OCCUPIED only, static cells never change, dyn_prev is the stage's own -- and the update is exact when it
+// is deferred: running it at t1 after t0 clears the blocks of t0 (which hold every DYNAMIC cell), marks and stores those of t1, which
+// is what the runs in between leave.  So in the whole-grid kernels (spec_full) a step that is not dyn-visible (include/d2d.h,
+// d2d_closed_loop) runs the perceive half with `dyn_skip` (run_env): no stage, and none of its feeders (st_agents_plain: the agents'
+// unit, previous block and new cell stay unloaded and unstaged).  The deferral needs a clean grid (dyn_gate_full): the env's
+// `dyn_gate` state, carried by the step loop in a scalar register like the episode flag, is 0 at the env's first step of a launch and
+// behind an in-kernel reset (the step then stages the feeders and tests the grid where the stage stands), 1 once the test has passed,
+// 2 when it failed or the launch defers nothing (D2D_OBS_EVERY_STEP=1, D2D_DONE_FREEZE, the window / tile kernels).
+// The form: ONE instantiation, with wave-uniform branches around the feeders and around the stage at the phase's tail, not a second
+// instantiation of run_env picked by a branch: that one (measured) gained half as much on the headline and cost
+// k_closed<2> 14 VGPRs and a spill.
+
 // The planner's every-step part AND the act phase in one call, for the steps whose trajectory is kept (96 % of them): the
 // planner's result reaches the control stage in registers -- no store -> fence -> load between the two, one call, one scalar-load
 // round trip for the arguments, one fence fewer per step.  Returns -1 when Primitive.plan has to search (the caller runs
@@ -2439,13 +2505,21 @@ __device__ __forceinline__ int ph_plan_act(const ClosedArgs *ap, int e_, int lds
 // gaze + the stages that follow it in one call (one set of callee-saved registers, one fence fewer per step)
 // `done_`: the env's episode flag as the caller knows it (the act phase of the step before returns it) -- no load, no round trip,
 // before the gaze stage can ask for anything else.  Returns the flag as this call's collision stage wrote it (-1: it did not run).
+// `dyn_gate`, `dyn_vis_`: the env's state of the deferred dynamic-grid update and whether this step is one the stage has to run on
+// anyway (dyn_skip).
 template <int SPEC, bool PDEF, uint32_t STAGES>
-__device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_off_, int t_, int done_) {
+__device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int lds_off_, int t_, int done_, int &dyn_gate, bool dyn_vis_) {
   const PhaseIn in_ = phase_enter(ap, e_, lds_off_);
   const ArgsPtr a = in_.a;
   const int e = in_.e, lane = in_.lane;
   int tstep = __builtin_amdgcn_readfirstlane(t_), known_done = __builtin_amdgcn_readfirstlane(done_);
   asm volatile("; phase" : "+s"(tstep), "+s"(known_done));
+  int dgate = 2;
+  const int dvis = dyn_vis_ ? 1 : 0;  // (a constant at the non-split site: its two instantiations keep one form of run_env each)
+  if constexpr (spec_full(SPEC)) {
+    dgate = __builtin_amdgcn_readfirstlane(dyn_gate);
+    asm volatile("; phase" : "+s"(dgate));
+  }
   char *base = d2d_lds + in_.off;
   d2d_cfg c = a->c;
   if (!spec_generic(SPEC)) spec_default_apply(c);
@@ -2469,7 +2543,12 @@ __device__ __forceinline__ int ph_gaze_stages(const ClosedArgs *ap, int e_, int 
   const size_t noise_off = c.noise_rows > 1 ? (size_t)((c.noise_row0 + tstep) % c.noise_rows) * c.B * c.N * 2 : 0;
   // (the plain order of loads, not run_env's one-batch form: with the agents' first pass held in registers across the grid copies
   // this phase saves 13 callee-saved registers per call instead of 6 -- 1.8 KB of scratch writes per env-step for +0.6 %)
-  run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, noise_off, false, nullptr, late_obs_of(STAGES));
+  if constexpr (spec_full(SPEC)) {
+    run_env<true, spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, noise_off, false, nullptr, late_obs_of(STAGES), &dgate, dvis != 0, dgate == 1 && dvis == 0);
+    dyn_gate = __builtin_amdgcn_readfirstlane(dgate);
+  } else {
+    run_env<spec_full(SPEC), spec_wide(SPEC), spec_cone(SPEC), spec_tiled(SPEC)>(c, a->s, e, lane, STAGES, g, L, a->s.action[e], r, noise_off, false, nullptr, late_obs_of(STAGES));
+  }
   if (lane == 0) store_regs(a->s, e, r);
   wave_sync_global();
 #ifdef D2D_CHAIN_PROF
@@ -2519,6 +2598,9 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
   const int nsteps = a->nsteps;
   const bool freeze = a->on_done == D2D_DONE_FREEZE;
   const bool obs_every = a->obs_every != 0;
+  // the deferred dynamic-grid update (dyn_skip): 0 -- the env's grid has yet to pass the gate, 2 -- the stage runs on every step
+  const bool dyn_defer = spec_full(SPEC) && !obs_every && !freeze, auto_reset = a->on_done == D2D_DONE_RESET;
+  int dyn_gate = dyn_defer ? 0 : 2;
   int nsearch = 0;
   int walls_ok = 0;  // (plan_env_quick: nothing is known about the trajectory's waypoints at the start of a launch)
 #ifdef D2D_CHAIN_PROF
@@ -2533,13 +2615,14 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
   for (int t = 0; t < nsteps; ++t) {
     if (freeze && flag_done != 0) break;  // one episode per env: it stays as it ended
     const bool visible = obs_every || t == nsteps - 1;  // (hidden_stages; wave-uniform: scalar operands only)
+    if (dyn_defer && auto_reset && flag_done != 0) dyn_gate = 0;  // this step starts from the snapshot: its grid is tested again
     if (split) {
       // An env that searches often is the one the launch ends up waiting for (the worlds repeat, so it stays that env):
       // past one search per 32 steps of this launch all its phases issue first on their SIMD.  Its chain is
       // latency-bound, so the three waves it shares the SIMD with give up little.  (+4 % at 4096 envs; thresholds 16-64
       // and levels 1-2 measure the same, level 3 -- the search's own -- less.)
       if (nsearch * 32 > t + 16) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
-      ph_gaze_stages<SPEC, PDEF, D2D_ST_PERCEIVE>(a, e, off, t, flag_done);
+      ph_gaze_stages<SPEC, PDEF, D2D_ST_PERCEIVE>(a, e, off, t, flag_done, dyn_gate, visible);
 #ifdef D2D_CHAIN_PROF
       const unsigned long long q0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -2570,8 +2653,8 @@ __global__ __launch_bounds__(WAVE *WAVES_PER_BLOCK, D2D_MIN_WAVES) void k_closed
         flag_done = pa;
       }
     } else {
-      flag_done = __builtin_amdgcn_readfirstlane(visible ? ph_gaze_stages<SPEC, PDEF, D2D_ST_ALL>(a, e, off, t, flag_done)
-                                                         : ph_gaze_stages<SPEC, PDEF, hidden_stages(D2D_ST_ALL)>(a, e, off, t, flag_done));
+      flag_done = __builtin_amdgcn_readfirstlane(visible ? ph_gaze_stages<SPEC, PDEF, D2D_ST_ALL>(a, e, off, t, flag_done, dyn_gate, true)
+                                                         : ph_gaze_stages<SPEC, PDEF, hidden_stages(D2D_ST_ALL)>(a, e, off, t, flag_done, dyn_gate, false));
     }
   }
 #ifdef D2D_CHAIN_PROF

@@ -435,7 +435,20 @@ int d2d_plan_stage(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan
  * nothing on the device reads the observation.  After the call every env therefore holds exactly the bytes it would hold had every
  * step written them.  D2D_OBS_EVERY_STEP=1 in the environment, read at every call, makes every step write the observation
  * (same-process A/B).  The per-stage path (plan->launch_args == NULL), d2d_rollout, d2d_run_stages and d2d_step write it on every
- * step. */
+ * step.
+ * Dynamic-grid visibility.  Nothing on the device reads what the dynamic-grid stage (D2D_ST_DYNGRID) writes -- rays and collision
+ * probes test gt for D2D_OCCUPIED only, dyn_prev is the stage's own -- and the update is exact when deferred: run at step t1 after
+ * step t0 it clears the blocks of t0, marks and stores those of t1, which is what the runs in between leave.  Inside the persistent
+ * launch of the default 50 x 50-cell geometry (both grids whole in LDS) an env's stage therefore runs only on a step that is
+ * dyn-visible: the last step of the call; every step when D2D_OBS_EVERY_STEP=1 (the same-process A/B switch of both rules); every
+ * step under D2D_DONE_FREEZE (a finished env's grid is its result); and every step of an env whose grid failed the gate.  The gate:
+ * deferring is exact only if (a) every cell of the env's gt holds D2D_OCCUPIED, D2D_UNOCCUPIED or D2D_DYNAMIC and (b) every
+ * D2D_DYNAMIC cell lies inside a block of its dyn_prev -- seeded worlds do, hand-edited grids may not.  The kernel tests both on the
+ * device at the env's first step of the call and again on the step behind an in-kernel reset (the snapshot's grid); an env that fails
+ * runs the stage on every step until its next reset or the end of the call.  After the call every byte of gt and dyn_prev equals what
+ * the every-step kernel leaves.  The persistent launches of other geometries (window / tile kernels), the per-stage path
+ * (plan->launch_args == NULL), d2d_rollout, d2d_run_stages, d2d_step, the stepped, stream and turn launches and every other library
+ * run the stage on every step. */
 int d2d_closed_loop(const d2d_cfg *cfg, const d2d_state *st, const d2d_plan *plan, int32_t nsteps,
                     int32_t on_done, const d2d_state *init, void *stream);
 
