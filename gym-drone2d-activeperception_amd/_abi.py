@@ -349,3 +349,26 @@ def bind_gaze(lib):
         'reset': (C.c_int, [V, V, I, I, V]),
     }
     return _bind(lib, 'd2d_gaze_', sig)
+
+
+# ---- include/d2d_seen.h: the time-since-observed map as an observation (csrc/seen/libd2d_seen.so, its own version) ----
+D2D_SEEN_VERSION = 1
+SEEN_POINTERS = ('seen', 'last_call', 'refreshed', 'obs', 'tab')
+SEEN_BUFFERS = ('seen', 'last_call', 'refreshed', 'obs')      # per env; `tab` is the host's table
+
+
+class Seen(C.Structure):
+    """include/d2d_seen.h `d2d_seen`."""
+    _fields_ = [(n, C.c_void_p) for n in SEEN_POINTERS] + [('acos_key_lo', C.c_int64), ('acos_mask', C.c_uint64)] + \
+               [('tab_len', C.c_int32), ('reserved', C.c_int32)]
+
+
+def bind_seen(lib):
+    """argtypes / restypes of include/d2d_seen.h on a loaded CDLL."""
+    P = C.POINTER
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'update': (C.c_int, [P(Cfg), P(State), P(Seen), C.c_void_p]),
+    }
+    return _bind(lib, 'd2d_seen_', sig)

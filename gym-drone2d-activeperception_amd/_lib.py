@@ -12,6 +12,7 @@ METRICS_LIB_PATH = os.path.join(_HERE, 'csrc', 'metrics', 'libd2d_metrics.so')  
 RVO_LIB_PATH = os.path.join(_HERE, 'csrc', 'rvo', 'libd2d_rvo.so')                      # include/d2d_rvo.h
 JERK_LIB_PATH = os.path.join(_HERE, 'csrc', 'jerk', 'libd2d_jerk.so')                   # include/d2d_jerk.h
 GAZE_LIB_PATH = os.path.join(_HERE, 'csrc', 'gaze', 'libd2d_gaze.so')                   # include/d2d_gaze.h
+SEEN_LIB_PATH = os.path.join(_HERE, 'csrc', 'seen', 'libd2d_seen.so')                   # include/d2d_seen.h
 
 
 class D2DError(RuntimeError):
@@ -37,6 +38,7 @@ _LIBRARIES = {
     'libd2d_rvo.so': (A.bind_rvo, 'version', 'D2D_RVO_VERSION', 'version', 'rvo/build.sh'),
     'libd2d_jerk.so': (A.bind_jerk, 'version', 'D2D_JERK_VERSION', 'version', 'jerk/build.sh'),
     'libd2d_gaze.so': (A.bind_gaze, 'version', 'D2D_GAZE_VERSION', 'version', 'gaze/build.sh'),
+    'libd2d_seen.so': (A.bind_seen, 'version', 'D2D_SEEN_VERSION', 'version', 'seen/build.sh'),
 }
 
 
@@ -85,6 +87,11 @@ def load_gaze_library(path=GAZE_LIB_PATH):
     return _load('libd2d_gaze.so', path)
 
 
+def load_seen_library(path=SEEN_LIB_PATH):
+    """The time-since-observed map as an observation channel, a library of its own (include/d2d_seen.h)."""
+    return _load('libd2d_seen.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -115,6 +122,7 @@ class HipBackend:
     supports_step_gaze = True             # include/d2d_gaze.h: LookAhead / Owl as a launch in front of the step (policy_step, run_episodes)
     supports_stepped_plugins = True       # include/d2d_stepped.h: the gaze and plan stages that leave finished envs alone (run_episodes)
     supports_rvo_live = True              # include/d2d_rvo_live.h: the RVO launches that leave finished envs alone (run_episodes)
+    supports_seen_obs = True              # include/d2d_seen.h: the time-since-observed map and its crop (VecDrone2DEnv(..., seen_obs=True))
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -132,6 +140,7 @@ class HipBackend:
         self.rlib = self.rfn = None       # libd2d_rvo.so: loaded by the first RVO call, likewise
         self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
         self.glib = self.gfn = None       # libd2d_gaze.so: loaded by the first gaze call of the step path, likewise
+        self.olib = self.ofn = None       # libd2d_seen.so: loaded by the first update of the time-since-observed map, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -409,6 +418,13 @@ class HipBackend:
     def gaze_reset(self, owl_state, mask=None, mask_stride=1):
         """d2d_gaze_reset: owl_state [B, OWL_STATE_F] float64 <- 0, for the envs of mask (or all)"""
         self._gaze('reset', owl_state.data_ptr(), None if mask is None else mask.data_ptr(), int(mask_stride), owl_state.shape[0])
+
+    def seen_update(self, cfg, st, seen):
+        """d2d_seen_update: `seen` is an _abi.Seen of device pointers (VecDrone2DEnv(..., seen_obs=True)); the envs whose step counter
+        has moved since their latest update get their map marked from the pose they are in, and its crop"""
+        if self.ofn is None:
+            self.olib, self.ofn = load_seen_library()
+        _check(self.ofn['update'](C.byref(cfg), C.byref(st), C.byref(seen), self._stream()), self.ofn, 'd2d_seen')
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

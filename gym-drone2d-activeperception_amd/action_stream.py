@@ -38,7 +38,8 @@ def restore_items(env, prev_cells=None):
     state.init_rvo leaves them (zero for the k = min(agent_number, N) seeded agents, the preferred velocity out of the `agents`
     planes for the static map's cell agents), the plan statistics and the storage no reset covers (trajectory, boxes, search nodes
     and hash, the scratch half of the velocity swap), the Jerk_Primitive choice and status, with swept_obs the swept map, its
-    crop and its count (include/d2d_swept.h) -- and `prev_cells`, the previous count
+    crop and its count (include/d2d_swept.h), with seen_obs the time-since-observed map's records and the call of its latest update
+    (include/d2d_seen.h) -- and `prev_cells`, the previous count
     of terms['explored'].  A buffer of no elements is left out."""
     s, items = env.state, []
 
@@ -70,6 +71,9 @@ def restore_items(env, prev_cells=None):
     if getattr(env, 'swept', None) is not None and len(env.swept) > 1:      # a rebuilt slot has a zero swept map at its step 0
         for name in ('map', 'obs', 'count'):
             zero('swept.' + name, env.swept[name])
+    if getattr(env, 'seen', None) is not None:                              # ... and a map on which nothing has been seen yet
+        for name in ('seen', 'last_call'):
+            zero('seen.' + name, env.seen[name])
     if prev_cells is not None:
         zero('explored_prev', prev_cells)
     return items
@@ -162,6 +166,7 @@ class ActionStream:
         items, n = self._item_array()
         b.stream_restore(items, n, self.refill)
         env.reset_plugins(self.refill)
+        env._seen_update()                     # a refilled slot's call 1 (its records are zero); every other slot's call has not moved
         return True
 
     # ------------------------------------------------------------------ the surface
@@ -169,7 +174,7 @@ class ActionStream:
         """`actions`: [B] float64 on the env's device, in [-1, 1] as VecDrone2DEnv.step takes them.  Returns (obs, terms, done, info):
         `obs` the dict of step() as views; `terms` device tensors [B]: newly_tracked, explored (this step's increase of the slot's
         discovered cells; the first step of a fresh world counts from 0), collision (0 none, 1 static, 2 dynamic: the flags byte of
-        the CSV row), goal, dead_lock, freezing; `done` [B] bool; `info`: live (the slot played an episode in this step), episode
+        the CSV row), goal, dead_lock, freezing, with seen_obs refreshed (VecDrone2DEnv.refreshed); `done` [B] bool; `info`: live (the slot played an episode in this step), episode
         (int32, the episode it played, -1 once retired), steps (the slot's step counter).  Everything but `done` is a view that the
         next call overwrites."""
         env, s = self.env, self.env.state
@@ -202,6 +207,8 @@ class ActionStream:
         torch.eq(s.counters[:, A.C_SM], A.SM_GOAL_REACHED, out=self.goal)
         terms = {'newly_tracked': s.newly, 'explored': self.explored, 'collision': s.flags[:, A.F_COLLISION], 'goal': self.goal,
                  'dead_lock': s.flags[:, A.F_DEADLOCK], 'freezing': s.flags[:, A.F_FREEZING]}
+        if env.seen is not None:               # the cells the slot's pose newly covered (include/d2d_seen.h)
+            terms['refreshed'] = env.seen['refreshed']
         info = {'live': self.live, 'episode': self.slot_episode, 'steps': s.counters[:, A.C_STEPS]}
         return obs, terms, done, info
 

@@ -188,6 +188,21 @@ def owl_table(params):
     return tab
 
 
+def tobs_table(params):
+    """[2][n_calls]: what a cell of Oxford.last_time_observed_map holds k calls after it was last seen (row 0: 0 + dt + dt ...) and
+    after k calls that never saw it (row 1: 5 + dt + dt ..., yaw_planner.py:48), by the reference's own additions (:95-97).  Shared
+    by the Oxford stage (`d2d_plan.tobs_tab`) and the time-since-observed channel (include/d2d_seen.h)."""
+    p = params
+    n_calls = int(math.ceil(p.max_flight_time / p.dt)) + 8
+    tab = np.zeros((2, n_calls), dtype=np.float64)
+    a0, a5 = 0.0, 5.0                                                            # :48 (5 * ones), :95-97
+    for k in range(n_calls):
+        tab[0, k], tab[1, k] = a0, a5
+        a0 = a0 + (1 - 0) * p.dt
+        a5 = a5 + (1 - 0) * p.dt
+    return tab
+
+
 def build_tables(params, cfg, need_acos=True, owl=False):
     """Scalars + numpy tables of `d2d_plan`, each computed as the reference computes it.  `need_acos`: the arccos decision
     window of the Oxford stage (view ranges it cannot describe only matter when that stage runs).  `owl`: the table of the Owl
@@ -211,14 +226,8 @@ def build_tables(params, cfg, need_acos=True, owl=False):
     # Oxford.__init__, yaw_planner.py:46-65
     w = p.drone_max_yaw_speed
     t['yaw_space'] = np.asarray(np.arange(-w, w, w / 3), dtype=np.float64)
-    n_calls = int(math.ceil(p.max_flight_time / p.dt)) + 8
-    tab = np.zeros((2, n_calls), dtype=np.float64)
-    a0, a5 = 0.0, 5.0                                                            # :48 (5 * ones), :95-97
-    for k in range(n_calls):
-        tab[0, k], tab[1, k] = a0, a5
-        a0 = a0 + (1 - 0) * p.dt
-        a5 = a5 + (1 - 0) * p.dt
-    t['tobs_tab'] = tab
+    t['tobs_tab'] = tab = tobs_table(p)
+    n_calls = tab.shape[1]
     leaves, prog = pairwise_plan(cfg.W * cfg.H)
     ops, lvl_start, root = pairwise_levels(len(leaves), prog)
     # per block: offset, length, first and last grid row it covers (the device walks rows)

@@ -252,7 +252,7 @@ def _grid_tile(params, backend, grid_layout):
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
                  kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None, redraw_agents=False,
-                 swept_obs=False):
+                 swept_obs=False, seen_obs=False):
         """`jerk_tie`: (tie_perm, tie_eq) for planner='Jerk_Primitive' in place of the table of this host's np.argsort
         (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it.
         `redraw_agents`: the worlds this env builds itself (worlds=None, worlds='device') are those of the validation study: every
@@ -262,7 +262,11 @@ class VecDrone2DEnv:
         `swept_obs`: obs['swep_map'] is the crop of the map Primitive.replan_check returned in the step (the cells the stored
         trajectory will pass through and when: envs/training_v3.py:141, :206-213, include/d2d_swept.h) instead of the explored map a
         second time (envs/drone_v2.py:252-253); `swept_map` and `swept_count` hold the full map and the waypoints marked.  The env then
-        steps through policy_step() / run_episodes() / action_stream() and stream_episodes(), one launch per stage."""
+        steps through policy_step() / run_episodes() / action_stream() and stream_episodes(), one launch per stage.
+        `seen_obs`: obs['age_map'] [B, 1, L, L] float32 is the crop of the time-since-observed map, what yaw_planner.Oxford keeps as
+        last_time_observed_map (yaw_planner.py:49, :92-97) and decides from, for the pose the env is in now, whichever planner and
+        gaze run (include/d2d_seen.h); `seen_calls`, `seen_age` and `refreshed` hold the full map and the cells the pose newly
+        covered.  One more launch behind every single step; closed_loop() and rollout(), whose steps nobody sees, refuse it."""
         self.params = with_defaults(params)
         self.redraw_agents = bool(redraw_agents)
         self.num_envs = int(num_envs)
@@ -411,6 +415,10 @@ class VecDrone2DEnv:
         self.swept = None                  # the buffers of include/d2d_swept.h (Jerk_Primitive: the crop alone, zero for ever)
         if self.swept_obs:
             self._init_swept(planner)
+        self.seen_obs = bool(seen_obs)
+        self.seen = None                   # the buffers of include/d2d_seen.h
+        if self.seen_obs:
+            self._init_seen()
 
     def _init_swept(self, planner):
         """The refusals and the buffers of swept_obs=True"""
@@ -466,6 +474,69 @@ class VecDrone2DEnv:
             elif t.numel():
                 t.masked_fill_(mask.bool().view((-1,) + (1,) * (t.dim() - 1)), 0)
 
+    def _init_seen(self):
+        """The refusals and the buffers of seen_obs=True, and the update of call 1: the map as the start pose sees it"""
+        import math
+        from .device_plugins import acos_window, tobs_table
+        backend_for(self.backend, None, 'supports_seen_obs', 'has no time-since-observed launch (include/d2d_seen.h: d2d_seen_update): '
+                    'seen_obs=True runs on the HIP backend, with csrc/seen/libd2d_seen.so built')
+        key_lo, mask = acos_window(math.radians(self.params.drone_view_range / 2))      # raises for a view range it cannot describe
+        B, L, dev = self.num_envs, self.cfg.L, self.device
+        tab = tobs_table(self.params)
+        i32 = torch.int32
+        self.seen = dict(seen=torch.zeros((B, self.cfg.W, self.cfg.H), dtype=i32, device=dev), last_call=torch.zeros(B, dtype=i32, device=dev),
+                         refreshed=torch.zeros(B, dtype=i32, device=dev), obs=torch.zeros((B, L, L), dtype=torch.float32, device=dev),
+                         tab=torch.from_numpy(tab).to(dev))
+        self._seen = A.Seen()
+        for n in A.SEEN_POINTERS:
+            t = self.seen[n]
+            setattr(self._seen, n, t.data_ptr() if t.numel() else self.state._dummy.data_ptr())
+        self._seen.acos_key_lo, self._seen.acos_mask, self._seen.tab_len, self._seen.reserved = key_lo, mask, tab.shape[1], 0
+        self._seen_update()
+
+    def _seen_update(self):
+        """d2d_seen_update: every env whose step counter has moved since its latest update (or that was zeroed) marks what its
+        pose sees and crops; a finished env, whose counter stands still, is left as it is"""
+        if self.seen is not None and self.num_envs:
+            self.backend.seen_update(self.cfg, self._st, self._seen)
+
+    def _seen_zero(self, mask=None):
+        """the map of a fresh world (Oxford.__init__, yaw_planner.py:49: nothing seen yet) for all envs or those of `mask`, then the
+        update of call 1 from the start pose; the other envs' calls have not moved, so the launch leaves them alone"""
+        if self.seen is None:
+            return
+        for n in ('seen', 'last_call'):
+            t = self.seen[n]
+            if mask is None:
+                t.zero_()
+            elif t.numel():
+                t.masked_fill_(mask.bool().view((-1,) + (1,) * (t.dim() - 1)), 0)
+        self._seen_update()
+
+    def _seen_needed(self, what):
+        if not self.seen_obs:
+            raise RuntimeError(f'{what}: build the env with seen_obs=True')
+
+    @property
+    def seen_calls(self):
+        """[B, W, H] int32: the number of the Oxford.plan() call (steps taken + 1) that last saw each cell, 0 = never"""
+        self._seen_needed('seen_calls')
+        return self.seen['seen']
+
+    @property
+    def seen_age(self):
+        """[B, W, H] float64: Oxford.last_time_observed_map as of each env's latest update, gathered from the table of the
+        reference's own additions (device_plugins.tobs_table)"""
+        self._seen_needed('seen_age')
+        sn, call, tab = self.seen['seen'].long(), self.seen['last_call'].long()[:, None, None], self.seen['tab']
+        return torch.where(sn > 0, tab[0][call - torch.minimum(sn.clamp(min=0), call)], tab[1][call.expand_as(sn)])
+
+    @property
+    def refreshed(self):
+        """[B] int32: the cells each env's latest update marked that the call before had not seen"""
+        self._seen_needed('refreshed')
+        return self.seen['refreshed']
+
     # ------------------------------------------------------------------ gym-like surface (batched)
     @property
     def N(self):
@@ -484,6 +555,7 @@ class VecDrone2DEnv:
             vel.copy_(vel0 if mask is None else torch.where(mask.bool()[:, None, None], vel0, vel))
         self.reset_plugins(mask)
         self._swept_zero(mask)
+        self._seen_zero(mask)
         return {}
 
     def _rvo_agents(self):
@@ -518,6 +590,7 @@ class VecDrone2DEnv:
             self.backend.run_stages(self.cfg, self._st, A.ST_ALL & ~A.ST_AGENTS)
         else:
             self.backend.step(self.cfg, self._st)
+        self._seen_update()
 
     def run_gaze(self):
         """d2d_gaze_act for every env that is not done: the action of the coming step, from what the previous step left.  The
@@ -576,6 +649,7 @@ class VecDrone2DEnv:
             self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
             if swept:
                 self.backend.swept_crop(self.cfg, self._st, self._swept)
+            self._seen_update()
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -584,7 +658,7 @@ class VecDrone2DEnv:
     def policy_step(self):
         """One step of the reference's episode loop (experiment.py:69-70): a = policy.plan(info), then env.step(a), with the policy
         on the device.  Returns what step() returns.  Oxford's own maps (the time since a cell was observed) are not kept: under
-        this planner they never reach an action, and nothing here makes them observable."""
+        this planner they never reach an action; seen_obs=True keeps the same map as a channel of its own (include/d2d_seen.h)."""
         self._needs_step_gaze('policy_step()')
         if self.plugins is not None:       # the Primitive plugins: one step of run_episodes' loop (an env that is done stays as it is)
             if self.num_envs:
@@ -659,6 +733,7 @@ class VecDrone2DEnv:
             else:
                 self.run_jerk_plan()
             self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
+            self._seen_update()
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -736,6 +811,7 @@ class VecDrone2DEnv:
         """Second half of step() (lines 198-255)."""
         self._set_action(actions)
         self.backend.act(self.cfg, self._st)
+        self._seen_update()
         return self._result()
 
     def rollout(self, actions, pin=None, collisions=False, streams=1):
@@ -744,6 +820,10 @@ class VecDrone2DEnv:
         `streams` > 1 cuts the batch into that many independent sub-batches whose T-step chains run on their own
         HIP streams (envs are independent, so the chains need no ordering between them; on MI355X two chains of
         2048 envs finish ~16 % sooner than one of 4096 because kernel tails and launch gaps overlap)."""
+        if self.seen is not None:
+            raise NotImplementedError('rollout(): seen_obs=True does not run inside a fused rollout (its steps would go unseen by the '
+                                      'time-since-observed map, whose launch of include/d2d_seen.h follows every single step); step '
+                                      'the env with step() / action_stream() / policy_step() / run_episodes()')
         actions = torch.as_tensor(actions, dtype=torch.float64, device=self.device).contiguous()
         T = actions.shape[0]
         assert actions.shape == (T, self.num_envs)
@@ -823,6 +903,8 @@ class VecDrone2DEnv:
                'yaw_angle': s.obs_yaw.unsqueeze(1)}
         if self.swept is not None:             # training_v3.py:206-213: the crop of what replan_check returned
             obs['swep_map'] = self.swept['obs'].unsqueeze(1)
+        if self.seen is not None:              # the crop of Oxford.last_time_observed_map for the pose the env is in
+            obs['age_map'] = self.seen['obs'].unsqueeze(1)
         done = s.flags[:, A.F_DONE].bool()
         info = {'collision_flag': s.flags[:, A.F_COLLISION], 'dead_lock_flag': s.flags[:, A.F_DEADLOCK],
                 'freezing_flag': s.flags[:, A.F_FREEZING], 'state_machine': s.counters[:, A.C_SM],
@@ -953,9 +1035,15 @@ class VecDrone2DEnv:
 
     def _episode_steps(self, n):
         """`n` steps of the env's own episode loop, finished envs left alone: closed_loop(freeze_done=True) where closed_loop() runs,
-        the step sequences of run_episodes() elsewhere -- and with swept_obs, whose map exists only between two stages of a step"""
+        the step sequences of run_episodes() elsewhere -- and with swept_obs, whose map exists only between two stages of a step.
+        With seen_obs, whose launch follows every single step, `n` times the path taken for n = 1"""
         if self.plugins is not None and not self.rvo and self.swept is None:
-            self.closed_loop(n, freeze_done=True)
+            if self.seen is None:
+                self.closed_loop(n, freeze_done=True)
+                return
+            for _ in range(n):             # the persistent launch, one step at a time
+                self._closed_loop_steps(1, A.DONE_FREEZE)
+                self._seen_update()
         elif self.plugins is not None:
             for _ in range(n):
                 self._plugins_step()
@@ -991,6 +1079,7 @@ class VecDrone2DEnv:
                 self.jerk.t[name].masked_fill_(m, 0)
         self._swept_zero(refill)
         self.reset_plugins(refill)
+        self._seen_zero(refill)
 
     def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
         """Episodes map_id + 0 .. map_id + num_episodes - 1 over the env's `num_envs` slots: a slot whose episode has ended is
@@ -1129,14 +1218,21 @@ class VecDrone2DEnv:
                                       'exists only between the perceive and the plan stage of a step, and the launches of '
                                       'include/d2d_swept.h go between them); step the env with action_stream() / policy_step() / '
                                       'run_episodes(), which run one launch per stage')
+        if self.seen is not None:
+            raise NotImplementedError('closed_loop(): seen_obs=True does not run inside the persistent closed loop (its steps would go '
+                                      'unseen by the time-since-observed map, whose launch of include/d2d_seen.h follows every single '
+                                      'step); step the env with action_stream() / policy_step() / run_episodes()')
         if auto_reset and self._streamed:
             raise RuntimeError('closed_loop(auto_reset=True): this env has streamed episodes (stream_episodes), so its slots hold other '
                                'worlds than the snapshot an auto reset restores; build a new VecDrone2DEnv for the map ids you want')
         mode = A.DONE_RESET if auto_reset else (A.DONE_FREEZE if freeze_done else A.DONE_CONTINUE)
-        self.backend.closed_loop(self.cfg, self._st, self._plan, int(nsteps), mode,
-                                 self._init_st if auto_reset else None)
-        self._advance_noise(nsteps)
+        self._closed_loop_steps(nsteps, mode)
         return self._result()
+
+    def _closed_loop_steps(self, nsteps, mode):
+        """d2d_closed_loop for `nsteps` steps under `mode` (DONE_*), the refusals of closed_loop() behind it"""
+        self.backend.closed_loop(self.cfg, self._st, self._plan, int(nsteps), mode, self._init_st if mode == A.DONE_RESET else None)
+        self._advance_noise(nsteps)
 
     def reset_plugins(self, mask=None):
         if self.plugins is not None:
