@@ -372,3 +372,25 @@ def bind_seen(lib):
         'update': (C.c_int, [P(Cfg), P(State), P(Seen), C.c_void_p]),
     }
     return _bind(lib, 'd2d_seen_', sig)
+
+
+# ---- include/d2d_scan.h: the per-ray scan of the raycast (csrc/scan/libd2d_scan.so, its own version) ----
+D2D_SCAN_VERSION = 1
+SCAN_POINTERS = ('pose', 'end', 'kind', 'hit', 'obs', 'last_step')
+SCAN_OUTPUTS = ('end', 'kind', 'hit', 'obs', 'last_step')     # what a reset or a refill clears; `pose` is the caller's snapshot
+
+
+class Scan(C.Structure):
+    """include/d2d_scan.h `d2d_scan`."""
+    _fields_ = [(n, C.c_void_p) for n in SCAN_POINTERS] + [('hit_words', C.c_int32), ('reserved', C.c_int32)]
+
+
+def bind_scan(lib):
+    """argtypes / restypes of include/d2d_scan.h on a loaded CDLL."""
+    P = C.POINTER
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'update': (C.c_int, [P(Cfg), P(State), P(Scan), C.c_void_p]),
+    }
+    return _bind(lib, 'd2d_scan_', sig)

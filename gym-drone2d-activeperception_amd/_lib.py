@@ -13,6 +13,7 @@ RVO_LIB_PATH = os.path.join(_HERE, 'csrc', 'rvo', 'libd2d_rvo.so')              
 JERK_LIB_PATH = os.path.join(_HERE, 'csrc', 'jerk', 'libd2d_jerk.so')                   # include/d2d_jerk.h
 GAZE_LIB_PATH = os.path.join(_HERE, 'csrc', 'gaze', 'libd2d_gaze.so')                   # include/d2d_gaze.h
 SEEN_LIB_PATH = os.path.join(_HERE, 'csrc', 'seen', 'libd2d_seen.so')                   # include/d2d_seen.h
+SCAN_LIB_PATH = os.path.join(_HERE, 'csrc', 'scan', 'libd2d_scan.so')                   # include/d2d_scan.h
 
 
 class D2DError(RuntimeError):
@@ -39,6 +40,7 @@ _LIBRARIES = {
     'libd2d_jerk.so': (A.bind_jerk, 'version', 'D2D_JERK_VERSION', 'version', 'jerk/build.sh'),
     'libd2d_gaze.so': (A.bind_gaze, 'version', 'D2D_GAZE_VERSION', 'version', 'gaze/build.sh'),
     'libd2d_seen.so': (A.bind_seen, 'version', 'D2D_SEEN_VERSION', 'version', 'seen/build.sh'),
+    'libd2d_scan.so': (A.bind_scan, 'version', 'D2D_SCAN_VERSION', 'version', 'scan/build.sh'),
 }
 
 
@@ -92,6 +94,11 @@ def load_seen_library(path=SEEN_LIB_PATH):
     return _load('libd2d_seen.so', path)
 
 
+def load_scan_library(path=SCAN_LIB_PATH):
+    """The per-ray scan of the raycast, a library of its own (include/d2d_scan.h)."""
+    return _load('libd2d_scan.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -123,6 +130,7 @@ class HipBackend:
     supports_stepped_plugins = True       # include/d2d_stepped.h: the gaze and plan stages that leave finished envs alone (run_episodes)
     supports_rvo_live = True              # include/d2d_rvo_live.h: the RVO launches that leave finished envs alone (run_episodes)
     supports_seen_obs = True              # include/d2d_seen.h: the time-since-observed map and its crop (VecDrone2DEnv(..., seen_obs=True))
+    supports_scan_obs = True              # include/d2d_scan.h: the per-ray scan of the raycast (VecDrone2DEnv(..., scan_obs=True))
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -141,6 +149,7 @@ class HipBackend:
         self.jlib = self.jfn = None       # libd2d_jerk.so: loaded by the first Jerk_Primitive call, likewise
         self.glib = self.gfn = None       # libd2d_gaze.so: loaded by the first gaze call of the step path, likewise
         self.olib = self.ofn = None       # libd2d_seen.so: loaded by the first update of the time-since-observed map, likewise
+        self.ylib = self.yfn = None       # libd2d_scan.so: loaded by the first update of the per-ray scan, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -425,6 +434,13 @@ class HipBackend:
         if self.ofn is None:
             self.olib, self.ofn = load_seen_library()
         _check(self.ofn['update'](C.byref(cfg), C.byref(st), C.byref(seen), self._stream()), self.ofn, 'd2d_seen')
+
+    def scan_update(self, cfg, st, scan):
+        """d2d_scan_update: `scan` is an _abi.Scan of device pointers (VecDrone2DEnv(..., scan_obs=True)); the envs whose step counter
+        has moved since their latest update get the rays of that step, cast from the pose snapshot over the agents as they stand"""
+        if self.yfn is None:
+            self.ylib, self.yfn = load_scan_library()
+        _check(self.yfn['update'](C.byref(cfg), C.byref(st), C.byref(scan), self._stream()), self.yfn, 'd2d_scan')
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

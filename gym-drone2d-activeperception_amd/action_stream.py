@@ -39,7 +39,7 @@ def restore_items(env, prev_cells=None):
     planes for the static map's cell agents), the plan statistics and the storage no reset covers (trajectory, boxes, search nodes
     and hash, the scratch half of the velocity swap), the Jerk_Primitive choice and status, with swept_obs the swept map, its
     crop and its count (include/d2d_swept.h), with seen_obs the time-since-observed map's records and the call of its latest update
-    (include/d2d_seen.h) -- and `prev_cells`, the previous count
+    (include/d2d_seen.h), with scan_obs the rays of the latest step and its counter (include/d2d_scan.h) -- and `prev_cells`, the previous count
     of terms['explored'].  A buffer of no elements is left out."""
     s, items = env.state, []
 
@@ -74,6 +74,9 @@ def restore_items(env, prev_cells=None):
     if getattr(env, 'seen', None) is not None:                              # ... and a map on which nothing has been seen yet
         for name in ('seen', 'last_call'):
             zero('seen.' + name, env.seen[name])
+    if getattr(env, 'scan', None) is not None:                              # ... and no rays yet (include/d2d_scan.h)
+        for name in A.SCAN_OUTPUTS:
+            zero('scan.' + name, env.scan[name])
     if prev_cells is not None:
         zero('explored_prev', prev_cells)
     return items

@@ -189,7 +189,7 @@ class DroneProxy:
         self.dt, self.params = p.dt, p
         self.map = GridProxy(env, 'dmap', p.map_scale, p.map_size)
         self.trackers = [TrackerProxy(env, k) for k in range(env._vec.N)]
-        self.rays = {}
+        self._rays, self._rays_pull = {}, -1
 
     def _num(self, i):
         v = float(self._env._mirror['drone'][i])
@@ -206,6 +206,37 @@ class DroneProxy:
     @property
     def radius(self):
         return self._env.params.drone_radius
+
+    @property
+    def rays(self):
+        """utils.py:726, :746: {} before the first step (and for ever without Drone2DEnv2(..., rays=True)); then the list of the
+        latest step's rays, {'coords': (x_hit, y_hit), 'wall': wall_hit, 'hit_list': int8[N]} each (utils.py:712), built from one
+        device-to-host copy when the attribute is read.  'wall' at a range stop is 2 where the reference has the raw map_gt value, 2
+        or -- on a cell that still carries the previous step's dynamic mark -- 3 (include/d2d_scan.h); nothing in the reference
+        reads it."""
+        env = self._env
+        vec = env._vec
+        if vec.scan is None:
+            return self._rays
+        if self._rays_pull != env._pull_count:
+            slot, N = env._slot, vec.N
+            parts = [vec.scan[k][slot].reshape(-1).view(torch.uint8) for k in ('end', 'hit', 'last_step', 'kind')]
+            flat = torch.cat(parts).cpu().numpy()
+            R, words = vec.cfg.R, vec._scan.hit_words
+            end = np.frombuffer(flat[:R * 16].tobytes(), dtype=np.float64).reshape(R, 2)
+            hit = np.frombuffer(flat[R * 16:R * 16 + R * words * 4].tobytes(), dtype=np.uint32).reshape(R, words)
+            last = int(np.frombuffer(flat[R * 16 + R * words * 4:R * 16 + R * words * 4 + 4].tobytes(), dtype=np.int32)[0])
+            kind = flat[R * 16 + R * words * 4 + 4:]
+            bits = ((hit[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(R, -1)[:, :N].astype(np.int8)
+            wall = (0, 1, 0, 2)
+            self._rays = [{'coords': (-1, -1) if kind[i] == 0 else (float(end[i, 0]), float(end[i, 1])), 'wall': wall[kind[i]],
+                           'hit_list': torch.from_numpy(bits[i].copy())} for i in range(R)] if last > 0 else {}
+            self._rays_pull = env._pull_count
+        return self._rays
+
+    @rays.setter
+    def rays(self, value):
+        self._rays, self._rays_pull = value, self._env._pull_count
 
     @property
     def velocity(self):
@@ -241,8 +272,10 @@ class Drone2DEnv2(_EnvBase):
                      'gt', 'dmap', 'active', 'hit', 'flags', 'obs_local')          # 8-byte fields first: aligned views
     _MIRROR_PLUGIN = ('trk_radius', 'traj_hdr')
 
-    def __init__(self, params, device='cuda:0', backend=None):
-        self._device, self._backend = device, backend
+    def __init__(self, params, device='cuda:0', backend=None, rays=False):
+        """`rays`: keep what every step's raycast found, ray by ray, as the reference's `env.drone.rays` (VecDrone2DEnv(...,
+        scan_obs=True), include/d2d_scan.h); the default keeps the constant {}."""
+        self._device, self._backend, self._keep_rays = device, backend, bool(rays)
         self._render_warned = False
         self._build(params)
 
@@ -261,7 +294,8 @@ class Drone2DEnv2(_EnvBase):
         plugins = self._mode in ('device', 'jerk') or want_gaze
         self._vec = VecDrone2DEnv(p, 1, device=self._device, backend=self._backend, grid_layout='rowmajor',   # the proxies index [W][H]
                                   planner=('Jerk_Primitive' if jerk else p.planner) if on_device else 'external',
-                                  device_plugins=plugins, gaze=('Oxford' if want_gaze else 'external') if plugins else None)
+                                  device_plugins=plugins, gaze=('Oxford' if want_gaze else 'external') if plugins else None,
+                                  scan_obs=self._keep_rays)
         self._slot = 0
         self._device_gaze = want_gaze
         self._backend = self._vec.backend
@@ -390,6 +424,9 @@ class Drone2DEnv2(_EnvBase):
         vec = self._vec
         if not (isinstance(a, DeviceAction) and a.fresh_for(self)):    # else: d2d_gaze_stage already wrote the action
             vec._set_action(float(a) if isinstance(a, DeviceAction) else float(np.asarray(a, dtype=np.float64).ravel()[0]))
+        fused = self._mode == 'fused' and not (self.params.var_cam != 0 and vec.N)
+        if not fused:                      # (run_step queues both itself)
+            vec._scan_snapshot()
         if self._mode == 'host':
             self._perceive()
             self._pull()
@@ -408,6 +445,7 @@ class Drone2DEnv2(_EnvBase):
             self._pull()
             return self._finish_step()
         vec.backend.act(vec.cfg, vec._st)
+        vec._scan_update()
         self._pull()
         return self._finish_step()
 

@@ -252,7 +252,7 @@ def _grid_tile(params, backend, grid_layout):
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
                  kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None, redraw_agents=False,
-                 swept_obs=False, seen_obs=False):
+                 swept_obs=False, seen_obs=False, scan_obs=False):
         """`jerk_tie`: (tie_perm, tie_eq) for planner='Jerk_Primitive' in place of the table of this host's np.argsort
         (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it.
         `redraw_agents`: the worlds this env builds itself (worlds=None, worlds='device') are those of the validation study: every
@@ -266,7 +266,12 @@ class VecDrone2DEnv:
         `seen_obs`: obs['age_map'] [B, 1, L, L] float32 is the crop of the time-since-observed map, what yaw_planner.Oxford keeps as
         last_time_observed_map (yaw_planner.py:49, :92-97) and decides from, for the pose the env is in now, whichever planner and
         gaze run (include/d2d_seen.h); `seen_calls`, `seen_age` and `refreshed` hold the full map and the cells the pose newly
-        covered.  One more launch behind every single step; closed_loop() and rollout(), whose steps nobody sees, refuse it."""
+        covered.  One more launch behind every single step; closed_loop() and rollout(), whose steps nobody sees, refuse it.
+        `scan_obs`: obs['scan'] [B, 2, R] float32 is the sensor's own reading, one range and one outcome per ray of the step's
+        raycast (include/d2d_scan.h); `ray_end`, `ray_kind` and `ray_hits` hold what the reference keeps as env.drone.rays
+        (utils.py:712, :746), bit for bit but for 'wall' at a range stop, which is 2 where the reference has the raw map_gt value (2,
+        or 3 on a cell that still carries the previous step's dynamic mark).  A copy of the pose in front of every single step and
+        one more launch behind it; no rays before the first step; closed_loop(n > 1) and rollout() refuse it."""
         self.params = with_defaults(params)
         self.redraw_agents = bool(redraw_agents)
         self.num_envs = int(num_envs)
@@ -419,6 +424,10 @@ class VecDrone2DEnv:
         self.seen = None                   # the buffers of include/d2d_seen.h
         if self.seen_obs:
             self._init_seen()
+        self.scan_obs = bool(scan_obs)
+        self.scan = None                   # the buffers of include/d2d_scan.h
+        if self.scan_obs:
+            self._init_scan()
 
     def _init_swept(self, planner):
         """The refusals and the buffers of swept_obs=True"""
@@ -537,6 +546,69 @@ class VecDrone2DEnv:
         self._seen_needed('refreshed')
         return self.seen['refreshed']
 
+    def _init_scan(self):
+        """The refusal and the buffers of scan_obs=True.  No launch: a fresh world has no rays yet (utils.py:726, `self.rays = {}`)"""
+        backend_for(self.backend, None, 'supports_scan_obs', 'has no per-ray scan launch (include/d2d_scan.h: d2d_scan_update): '
+                    'scan_obs=True runs on the HIP backend, with csrc/scan/libd2d_scan.so built')
+        B, R, dev = self.num_envs, self.cfg.R, self.device
+        words = max(1, (self.cfg.N + 31) // 32)
+        self.scan = dict(pose=torch.zeros((B, A.DF), dtype=torch.float64, device=dev), end=torch.zeros((B, R, 2), dtype=torch.float64, device=dev),
+                         kind=torch.zeros((B, R), dtype=torch.uint8, device=dev), hit=torch.zeros((B, R, words), dtype=torch.int32, device=dev),
+                         obs=torch.zeros((B, 2, R), dtype=torch.float32, device=dev), last_step=torch.zeros(B, dtype=torch.int32, device=dev))
+        self._scan = A.Scan()
+        for n in A.SCAN_POINTERS:
+            t = self.scan[n]
+            setattr(self._scan, n, t.data_ptr() if t.numel() else self.state._dummy.data_ptr())
+        self._scan.hit_words, self._scan.reserved = words, 0
+
+    def _scan_snapshot(self):
+        """the pose the coming step's rays are cast from (drone_v2.py:173 runs before step_pos / step_yaw): queued in front of the
+        step's first launch"""
+        if self.scan is not None:
+            self.scan['pose'].copy_(self.state.drone)
+
+    def _scan_update(self):
+        """d2d_scan_update: every env whose step counter has moved since its latest update gets the rays of that step; a finished
+        env, whose counter stands still, and a world that has not stepped are left as they are"""
+        if self.scan is not None and self.num_envs:
+            self.backend.scan_update(self.cfg, self._st, self._scan)
+
+    def _scan_zero(self, mask=None):
+        """no rays yet (utils.py:726) for all envs or those of `mask`: a slot whose previous episode ended at step k would otherwise
+        be skipped at step k of its next one"""
+        if self.scan is None:
+            return
+        for n in A.SCAN_OUTPUTS:
+            t = self.scan[n]
+            if mask is None:
+                t.zero_()
+            elif t.numel():
+                t.masked_fill_(mask.bool().view((-1,) + (1,) * (t.dim() - 1)), 0)
+
+    def _scan_needed(self, what):
+        if not self.scan_obs:
+            raise RuntimeError(f'{what}: build the env with scan_obs=True')
+
+    @property
+    def ray_end(self):
+        """[B, R, 2] float64: 'coords' of every ray of the latest step (utils.py:712), (-1, -1) where the ray did not stop"""
+        self._scan_needed('ray_end')
+        return self.scan['end']
+
+    @property
+    def ray_kind(self):
+        """[B, R] uint8: 0 no stop, 1 an OCCUPIED cell, 2 inside an agent, 3 the range (include/d2d_scan.h)"""
+        self._scan_needed('ray_kind')
+        return self.scan['kind']
+
+    @property
+    def ray_hits(self):
+        """[B, R, N] bool: 'hit_list' of every ray, unpacked from the words on demand"""
+        self._scan_needed('ray_hits')
+        h = self.scan['hit']
+        bits = (h.unsqueeze(-1) >> torch.arange(32, dtype=torch.int32, device=h.device)) & 1
+        return bits.reshape(h.shape[0], h.shape[1], -1)[:, :, :self.cfg.N].bool()
+
     # ------------------------------------------------------------------ gym-like surface (batched)
     @property
     def N(self):
@@ -556,6 +628,7 @@ class VecDrone2DEnv:
         self.reset_plugins(mask)
         self._swept_zero(mask)
         self._seen_zero(mask)
+        self._scan_zero(mask)
         return {}
 
     def _rvo_agents(self):
@@ -581,6 +654,7 @@ class VecDrone2DEnv:
     def run_step(self):
         """d2d_step with the action already set; under RVO the agents move first, then every other stage (the state machine stage,
         which d2d_step runs before the agents, does not touch them: the order is the reference's)"""
+        self._scan_snapshot()
         if self.jerk is not None:
             self.run_perceive()
             self.run_jerk_plan()
@@ -591,6 +665,7 @@ class VecDrone2DEnv:
         else:
             self.backend.step(self.cfg, self._st)
         self._seen_update()
+        self._scan_update()
 
     def run_gaze(self):
         """d2d_gaze_act for every env that is not done: the action of the coming step, from what the previous step left.  The
@@ -633,6 +708,7 @@ class VecDrone2DEnv:
         `before_plan()`, a hook for tests, is called behind the mark with everything it read still in place"""
         noise = self.state.noise if self.cfg.noise_rows > 1 else None
         swept = self.swept is not None
+        self._scan_snapshot()
         try:
             if self._plan.gaze != A.GAZE_NONE:
                 self.backend.gaze_stage_live(self.cfg, self._st, self._plan)
@@ -650,6 +726,7 @@ class VecDrone2DEnv:
             if swept:
                 self.backend.swept_crop(self.cfg, self._st, self._swept)
             self._seen_update()
+            self._scan_update()
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -721,6 +798,7 @@ class VecDrone2DEnv:
         SKIP_DONE).  `live`: the plan and RVO launches that leave finished envs alone (include/d2d_jerk_live.h, d2d_rvo_live.h),
         else the unmasked ones"""
         noise = self.state.noise if self.cfg.noise_rows > 1 else None
+        self._scan_snapshot()
         try:
             self.run_gaze()
             if noise is not None:                     # as rollout(): a single d2d_run_stages reads the block's first row
@@ -734,6 +812,7 @@ class VecDrone2DEnv:
                 self.run_jerk_plan()
             self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
             self._seen_update()
+            self._scan_update()
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -802,10 +881,12 @@ class VecDrone2DEnv:
 
     def perceive(self):
         """First half of step() (lines 153-187); a host planner plugin runs after this (the device Jerk_Primitive planner runs
-        here, as the last part of this half)."""
+        here, as the last part of this half).  With scan_obs the rays are ready behind this half: the pose has not moved yet."""
+        self._scan_snapshot()
         self.run_perceive()
         if self.jerk is not None:
             self.run_jerk_plan()
+        self._scan_update()
 
     def act(self, actions):
         """Second half of step() (lines 198-255)."""
@@ -823,6 +904,10 @@ class VecDrone2DEnv:
         if self.seen is not None:
             raise NotImplementedError('rollout(): seen_obs=True does not run inside a fused rollout (its steps would go unseen by the '
                                       'time-since-observed map, whose launch of include/d2d_seen.h follows every single step); step '
+                                      'the env with step() / action_stream() / policy_step() / run_episodes()')
+        if self.scan is not None:
+            raise NotImplementedError('rollout(): scan_obs=True does not run inside a fused rollout (the rays of its steps would be gone: '
+                                      'the launch of include/d2d_scan.h follows every single step, from the pose in front of it); step '
                                       'the env with step() / action_stream() / policy_step() / run_episodes()')
         actions = torch.as_tensor(actions, dtype=torch.float64, device=self.device).contiguous()
         T = actions.shape[0]
@@ -905,6 +990,8 @@ class VecDrone2DEnv:
             obs['swep_map'] = self.swept['obs'].unsqueeze(1)
         if self.seen is not None:              # the crop of Oxford.last_time_observed_map for the pose the env is in
             obs['age_map'] = self.seen['obs'].unsqueeze(1)
+        if self.scan is not None:              # one range and one outcome per ray of the latest step's raycast
+            obs['scan'] = self.scan['obs']
         done = s.flags[:, A.F_DONE].bool()
         info = {'collision_flag': s.flags[:, A.F_COLLISION], 'dead_lock_flag': s.flags[:, A.F_DEADLOCK],
                 'freezing_flag': s.flags[:, A.F_FREEZING], 'state_machine': s.counters[:, A.C_SM],
@@ -1038,12 +1125,14 @@ class VecDrone2DEnv:
         the step sequences of run_episodes() elsewhere -- and with swept_obs, whose map exists only between two stages of a step.
         With seen_obs, whose launch follows every single step, `n` times the path taken for n = 1"""
         if self.plugins is not None and not self.rvo and self.swept is None:
-            if self.seen is None:
+            if self.seen is None and self.scan is None:
                 self.closed_loop(n, freeze_done=True)
                 return
             for _ in range(n):             # the persistent launch, one step at a time
+                self._scan_snapshot()
                 self._closed_loop_steps(1, A.DONE_FREEZE)
                 self._seen_update()
+                self._scan_update()
         elif self.plugins is not None:
             for _ in range(n):
                 self._plugins_step()
@@ -1080,6 +1169,7 @@ class VecDrone2DEnv:
         self._swept_zero(refill)
         self.reset_plugins(refill)
         self._seen_zero(refill)
+        self._scan_zero(refill)
 
     def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
         """Episodes map_id + 0 .. map_id + num_episodes - 1 over the env's `num_envs` slots: a slot whose episode has ended is
@@ -1222,11 +1312,17 @@ class VecDrone2DEnv:
             raise NotImplementedError('closed_loop(): seen_obs=True does not run inside the persistent closed loop (its steps would go '
                                       'unseen by the time-since-observed map, whose launch of include/d2d_seen.h follows every single '
                                       'step); step the env with action_stream() / policy_step() / run_episodes()')
+        if self.scan is not None and (int(nsteps) > 1 or auto_reset):
+            raise NotImplementedError('closed_loop(): scan_obs=True takes one step a call and no auto_reset (inside the persistent loop the '
+                                      'rays of its steps would be gone: the launch of include/d2d_scan.h follows every single step, from '
+                                      'the pose in front of it); step the env with action_stream() / policy_step() / run_episodes()')
         if auto_reset and self._streamed:
             raise RuntimeError('closed_loop(auto_reset=True): this env has streamed episodes (stream_episodes), so its slots hold other '
                                'worlds than the snapshot an auto reset restores; build a new VecDrone2DEnv for the map ids you want')
         mode = A.DONE_RESET if auto_reset else (A.DONE_FREEZE if freeze_done else A.DONE_CONTINUE)
+        self._scan_snapshot()
         self._closed_loop_steps(nsteps, mode)
+        self._scan_update()                # (a single step: more are refused above)
         return self._result()
 
     def _closed_loop_steps(self, nsteps, mode):
