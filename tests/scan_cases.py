@@ -172,28 +172,33 @@ def handmade_poses(W_px, H_px):
             P(cx, cy, 10, 5, 5), P(cx, cy, 10, 0, 0), P(W_px - 11.5, H_px - 12.5, 77.7, 9, 0)]
 
 
-def run_handmade(env, launch, record=None):
+def run_handmade(env, launch, record=None, poses=None, place=None):
     """The poses through `launch()` -- one d2d_scan_update over the env's own structs -- with every buffer the launch may write
     poisoned first, against the model; then a second launch without a step, which must change nothing.  The state and dmap must
-    come out as they went in.  Returns (envs left alone, rays per kind)"""
+    come out as they went in.  `poses`: handmade_poses unless given; `place(agents, walls, poses)`: writes a set's own agents into the
+    planes [B, AF, N] and walls into the grids [B, bytes] (the crowd and the ring below).  Returns (envs left alone, rays per kind)"""
     import torch
-    import scan_backend as SB
     from drone2d_amd import _abi as A
     cfg, B = env.cfg, env.num_envs
-    poses = handmade_poses(cfg.W_px, cfg.H_px)
+    poses = handmade_poses(cfg.W_px, cfg.H_px) if poses is None else poses
     assert B == len(poses) == 16
     N, R, hw = cfg.N, cfg.R, env._scan.hit_words
-    rs = np.random.RandomState(5)
     agents, counters = env.state.agents.cpu().numpy().copy(), env.state.counters.cpu().numpy().copy()
     pose = np.zeros((B, A.DF), dtype=np.float64)
     last = np.zeros(B, dtype=np.int32)
     for e, q in enumerate(poses):
         pose[e, A.D_X], pose[e, A.D_Y], pose[e, A.D_YAW] = q['x'], q['y'], q['yaw']
         counters[e, A.C_STEPS], last[e] = q['steps'], q['last']
+        if place is not None:
+            continue
         for k in range(min(q['inside'], N)):       # agents whose circle holds the drone: the ray ends at sample 0 with all of them
             agents[e, A.A_PX, k], agents[e, A.A_PY, k] = q['x'] + 4.0 * k - 1.0, q['y'] + 2.0
         if N > 40:                                 # agent 70 in the way of the straight-ahead rays: a bit of the third word
             agents[e, A.A_PX, 70], agents[e, A.A_PY, 70] = q['x'] + 40.0 * np.cos(np.radians(q['yaw'])), q['y'] - 40.0 * np.sin(np.radians(q['yaw']))
+    if place is not None:
+        walls = env.state.gt.cpu().numpy().reshape(B, -1).copy()
+        place(agents, walls, poses)
+        env.state.gt.copy_(torch.from_numpy(walls).reshape(env.state.gt.shape).to(env.device))
     poison = lambda shape, dt: np.frombuffer(np.full(int(np.prod(shape)) * np.dtype(dt).itemsize, POISON, dtype=np.uint8).tobytes(), dtype=dt).reshape(shape).copy()   # noqa: E731
     before = dict(end=poison((B, R, 2), np.float64), kind=poison((B, R), np.uint8), hit=poison((B, R, hw), np.int32),
                   obs=poison((B, 2, R), np.float32), last_step=last)
@@ -235,6 +240,148 @@ def run_handmade(env, launch, record=None):
     if record is not None:
         record.append(dict(cfg=cfg, hit_words=hw, agents=agents, counters=counters, gt=gt, pose=pose, before=before, want=got))
     return alone, tuple(int(v) for v in kinds)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the crowd, the ring
+CCAP = 64                            # D2D_SCAN_CCAP of csrc/scan/d2d_scan.h: an env with more candidates tests every agent
+CROWD_COUNTS = (63, 64, 65, 72)      # candidates of env e: CROWD_COUNTS[e % 4] -- below, at and above the list's capacity, and everyone
+CROWD_N = 72                         # three hit words
+CROWD_R2 = 2.5 ** 2                  # small circles: a ray of such a crowd can pass between them (radius 15 stops every ray in an agent)
+RING_N = 33                          # d = 0, 0.5 .. 16 px beyond radius + depth
+RING_RADIUS = 5.0
+
+
+def near(px, py, r2, x0, y0, depth, ss):
+    """the documented cull bound of d2d_scan_near (csrc/scan/d2d_scan.h), restated: may this agent hold a sample of the drone's rays?"""
+    lim = np.sqrt(r2) + depth + 1.5 * ss + 2.0
+    dx, dy = px - x0, py - y0
+    return dx * dx + dy * dy <= lim * lim
+
+
+def candidates(cfg, pose, agents):
+    """[B] the candidates of every env under `near`, [B, N] which they are"""
+    from drone2d_amd import _abi as A
+    ss = float(cfg.scale) - 1.0
+    is_near = near(agents[:, A.A_PX], agents[:, A.A_PY], agents[:, A.A_R2], pose[:, A.D_X, None], pose[:, A.D_Y, None], float(cfg.depth), ss)
+    return is_near.sum(axis=1), is_near
+
+
+def crowd_params(pkg):
+    return pkg.Params(planner='NoMove', agent_number=CROWD_N, agent_radius=15, agent_max_speed=20, map_id=3, map_size=[500, 500],
+                      init_pos=[50, 50], target_list=[[450, 450]]), 'tiled'
+
+
+def ring_params(pkg):
+    return pkg.Params(planner='NoMove', agent_number=RING_N, agent_radius=15, agent_max_speed=20, map_id=3, map_size=[500, 500],
+                      init_pos=[50, 50], target_list=[[450, 450]]), 'rowmajor'
+
+
+CROWD_AT = (260.0, 240.0)            # a cell's origin near the centre
+CROWD_WALLS = ((5, 0), (-5, 0), (0, 5), (0, -5), (4, 4), (-4, 4), (4, -4), (-4, -4))      # cells from the drone's: within the range
+
+
+def crowd_poses(W_px, H_px):
+    """16 envs at one cell's origin near the centre, yaw 22.5 * e: the four envs of a candidate count (e % 4) look into all four
+    quadrants"""
+    return [dict(x=CROWD_AT[0], y=CROWD_AT[1], yaw=22.5 * e, steps=1 + e % 3, last=0, inside=0) for e in range(16)]
+
+
+def crowd_place(cfg):
+    """place(agents, walls, poses) of the crowd: env e has CROWD_COUNTS[e % 4] agents scattered within the range of its drone -- three
+    of them laid over three others, so that a sample lies in two -- and the rest parked in the far corner.  The parked ones have
+    indices below 64 (another choice in every env), so agents 64 .. 71 are candidates everywhere: the second pass of the device's
+    cull always adds to the list, up to slot 63 exactly in the envs of 64 candidates and past it in those of 65.  Map 3 has walls on
+    its border alone, farther from the centre than the range: eight OCCUPIED cells go around the drone, with gaps between them"""
+    from drone2d_amd import _abi as A
+    depth = float(cfg.depth)
+
+    def place(agents, walls, poses):
+        rs = np.random.RandomState(72)
+        N = agents.shape[2]
+        assert N == CROWD_N
+        for e, q in enumerate(poses):
+            parked = sorted({(3 * e + 5 * j) % 64 for j in range(N - CROWD_COUNTS[e % 4])})
+            assert len(parked) == N - CROWD_COUNTS[e % 4]
+            rho, phi = depth * np.sqrt(rs.uniform(0.01, 1.0, N)), rs.uniform(0, 2 * np.pi, N)
+            agents[e, A.A_PX], agents[e, A.A_PY] = q['x'] + rho * np.cos(phi), q['y'] + rho * np.sin(phi)
+            for k in (64, 66, 68):                 # pairs a sample can lie in together: bits of the third word with a neighbour's
+                agents[e, A.A_PX, k + 1], agents[e, A.A_PY, k + 1] = agents[e, A.A_PX, k] + 1.0, agents[e, A.A_PY, k] - 0.5
+            agents[e, A.A_R2] = CROWD_R2
+            for j, k in enumerate(parked):
+                agents[e, A.A_PX, k], agents[e, A.A_PY, k] = 3.0 + 2.0 * (j % 4), 3.0 + 2.0 * (j // 4)
+            ci, cj = int(q['x'] // cfg.scale), int(q['y'] // cfg.scale)
+            for di, dj in CROWD_WALLS:
+                walls[e, SN.grid_index(ci + di, cj + dj, cfg.H, cfg.grid_tile)] = A.OCCUPIED
+    return place
+
+
+def check_crowd(cfg, rec):
+    """the record run_handmade left of the crowd is what the set is for: the candidate counts under the documented bound (a later
+    change of the bound fails here, it does not turn the case back into the small-list path), agents 64 .. 71 among the candidates of
+    every env, and by the model alone rays of every kind a drone inside the map can have -- stopped by a wall, by an agent and by the
+    range (kind 0 is a ray that leaves the map: with the range at 80 px none of a drone at the centre does) -- in every group, some
+    of them inside two agents at once"""
+    count, is_near = candidates(cfg, rec['pose'], rec['agents'])
+    assert count.tolist() == [CROWD_COUNTS[e % 4] for e in range(16)], count.tolist()
+    assert is_near[:, 64:].all()
+    kind, hit = rec['want']['kind'], rec['want']['hit']
+    for g in range(4):
+        kinds = np.bincount(kind[g::4].reshape(-1), minlength=4)
+        assert kinds[0] == 0 and kinds[1] >= 1 and kinds[2] >= 1 and kinds[3] >= 1, (g, kinds.tolist())
+        assert int((popcount(hit[g::4]) >= 2).sum()) >= 1, g
+        assert hit[g::4, :, 2].any(), g            # an agent of index >= 64 was met
+
+
+def ring_poses(W_px, H_px):
+    """16 envs at the centre cell's origin, yaws 0, 7.3 .. 109.5: the step of a ray is 9 .. 12.7 px long, so its last sample lies
+    0 .. 12.7 px beyond the range"""
+    return [dict(x=250.0, y=250.0, yaw=7.3 * e, steps=1, last=0, inside=0) for e in range(16)]
+
+
+def ring_place(cfg):
+    """place(agents, walls, poses) of the ring: agent k of env e is centred on ray (7 k + 3 e) % R at distance radius + depth + k / 2 from the
+    drone, k = 0 .. 32.  The last sample of a ray lies up to a step beyond the range, so a circle whose rim is that far out holds a
+    genuine sample; a cull bound that is too tight drops it, one that is right keeps every agent the model's loop over all agents meets"""
+    from drone2d_amd import _abi as A
+
+    def place(agents, walls, poses):
+        N = agents.shape[2]
+        assert N == RING_N
+        for e, q in enumerate(poses):
+            for k in range(N):
+                i = (7 * k + 3 * e) % cfg.R
+                ang = SN.positive_angle((np.pi * 2 - q['yaw'] * (np.pi / 180)) + float(cfg.ray_off0) + float(cfg.ray_dth) * i)
+                dist = RING_RADIUS + float(cfg.depth) + 0.5 * k
+                agents[e, A.A_PX, k], agents[e, A.A_PY, k] = q['x'] + dist * np.cos(ang), q['y'] + dist * np.sin(ang)
+            agents[e, A.A_R2] = RING_RADIUS ** 2
+    return place
+
+
+def check_ring(cfg, rec):
+    """the ring is at the bound: agents on either side of it, and by the model alone hits of agents whose rim is more than half a
+    step (+ 2 px) beyond the range -- the ones a bound of depth + 0.5 * (scale - 1) + 2 would have dropped"""
+    count, is_near = candidates(cfg, rec['pose'], rec['agents'])
+    assert 0 < count.min() and count.max() < RING_N and (count <= CCAP).all(), count.tolist()
+    met = unpack(np.bitwise_or.reduce(rec['want']['hit'], axis=1), RING_N)            # [B, N]: the agents some ray of the env met
+    beyond = 0.5 * np.arange(RING_N)
+    ss = float(cfg.scale) - 1.0
+    assert int(met[:, beyond > 0.5 * ss + 2.0].sum()) >= 8, met.sum(axis=0).tolist()
+    assert not met[~is_near].any()                 # the documented bound itself drops nobody the model meets
+    return int(met.sum())
+
+
+SPECIAL = {'crowd': (crowd_params, crowd_poses, crowd_place, check_crowd), 'ring': (ring_params, ring_poses, ring_place, check_ring)}
+
+
+def run_special(env, name, launch, record=None):
+    """the crowd or the ring through run_handmade, then the set's own coverage check on the record"""
+    _, poses, place, check = SPECIAL[name]
+    rec = []
+    out = run_handmade(env, launch, rec, poses=poses(env.cfg.W_px, env.cfg.H_px), place=place(env.cfg))
+    check(env.cfg, rec[0])
+    if record is not None:
+        record.extend(rec)
+    return out
 
 
 def check_cleared(env, e):

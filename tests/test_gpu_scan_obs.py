@@ -52,6 +52,19 @@ def test_handmade_poses_through_the_launch_alone(pkg, hip, k):
     assert alone == 2 and kinds[0] >= 2 * env.cfg.R and kinds[1] > 0 and kinds[3] > 0 and (kinds[2] >= 2 * env.cfg.R) == (n >= 2)
 
 
+@pytest.mark.parametrize('name', list(SC.SPECIAL))
+def test_the_crowd_and_the_ring_through_the_launch_alone(pkg, hip, name):
+    """the crowd: 16 envs of 63, 64, 65 and 72 candidates among 72 agents -- the LDS list one short of its capacity, exactly full
+    (the `slot < D2D_SCAN_CCAP` guard at 64, the second ballot pass filling slots up to 63) and overflowing (the kernel tests every
+    agent from global memory, cidx == nullptr); the ring: agents centred 0 .. 16 px beyond radius + depth along ray directions,
+    either side of the cull bound.  Poisoned buffers, the model without a cull of its own, a second launch that changes nothing"""
+    p, layout = SC.SPECIAL[name][0](pkg)
+    env = _env(hip, p, 16, scan_obs=True, device_plugins=False, gaze=None, grid_layout=layout)
+    assert (env.cfg.W, env.cfg.H, env.cfg.N, env._scan.hit_words) == (50, 50, p.agent_number, (p.agent_number + 31) // 32)
+    alone, kinds = SC.run_special(env, name, lambda: hip.scan_update(env.cfg, env._st, env._scan))
+    assert alone == 0 and sum(kinds) == 16 * env.cfg.R and kinds[2] > 0 and kinds[3] > 0
+
+
 # ---------------------------------------------------------------------------------------------------------------- 3. config 5
 @pytest.mark.parametrize('layout', ['rowmajor', 'tiled'])
 def test_config_5_geometry(pkg, hip, layout):

@@ -208,12 +208,26 @@ def _handmade_env(pkg, k):
     return env
 
 
+def _special_env(pkg, name):
+    p, layout = SC.SPECIAL[name][0](pkg)
+    env = SB.env_of(p, 16, scan_obs=True, planner=p.planner, device_plugins=False, gaze=None, grid_layout=layout)
+    assert (env.cfg.W, env.cfg.H, env.cfg.N, env._scan.hit_words) == (50, 50, p.agent_number, (p.agent_number + 31) // 32)
+    return env
+
+
 HANDMADE_ALONE = 2       # the finished env and the env with counter 0
 
 
 @host_build.needs_fma('csrc/scan/d2d_scan.h restates a libm tan that fuses multiply-adds (-mfma)')
-@pytest.mark.parametrize('k', range(len(SC.HANDMADE)))
+@pytest.mark.parametrize('k', list(range(len(SC.HANDMADE))) + list(SC.SPECIAL))
 def test_the_host_build_against_the_model_on_the_handmade_poses(pkg, host, k):
+    """... and on the crowd (63, 64, 65 and 72 candidates: the culled list below and at its capacity, and the fallback to every
+    agent above it) and the ring at the cull bound, tests/scan_cases.SPECIAL"""
+    if k in SC.SPECIAL:
+        env = _special_env(pkg, k)
+        alone, kinds = SC.run_special(env, k, lambda: host.scan_host_update(C.byref(env.cfg), C.byref(env._st), C.byref(env._scan)))
+        assert alone == 0 and sum(kinds) == 16 * env.cfg.R and kinds[2] > 0 and kinds[3] > 0
+        return
     env = _handmade_env(pkg, k)
 
     def launch():
@@ -242,14 +256,19 @@ def test_the_host_build_replays_an_episode(pkg, host):
 
 @host_build.needs_fma('csrc/scan/d2d_scan.h restates a libm tan that fuses multiply-adds (-mfma)')
 def test_the_host_build_under_the_sanitizers(pkg, host, tmp_path):
-    """the handmade sets through a stand-alone program built with AddressSanitizer and UBSan, on exactly sized heap arrays: every
-    index the loop forms -- the grid in either layout, the last ray's last hit word, the candidate list -- stays inside its array"""
+    """the handmade sets, the crowd and the ring through a stand-alone program built with AddressSanitizer and UBSan, on exactly
+    sized heap arrays: every index the loop forms -- the grid in either layout, the last ray's last hit word, the candidate list at
+    its capacity and the agents' planes behind the fallback -- stays inside its array"""
     import struct
     import subprocess
     records = []
     for k in range(len(SC.HANDMADE)):
         env = _handmade_env(pkg, k)
         SC.run_handmade(env, lambda: host.scan_host_update(C.byref(env.cfg), C.byref(env._st), C.byref(env._scan)), records)
+    for name in SC.SPECIAL:
+        env = _special_env(pkg, name)
+        SC.run_special(env, name, lambda: host.scan_host_update(C.byref(env.cfg), C.byref(env._st), C.byref(env._scan)), records)
+    assert len(records) == len(SC.HANDMADE) + 2
     path = tmp_path / 'records.bin'
     with open(path, 'wb') as f:
         f.write(struct.pack('<i', len(records)))
