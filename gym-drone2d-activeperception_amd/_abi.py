@@ -394,3 +394,26 @@ def bind_scan(lib):
         'update': (C.c_int, [P(Cfg), P(State), P(Scan), C.c_void_p]),
     }
     return _bind(lib, 'd2d_scan_', sig)
+
+
+# ---- include/d2d_tracks.h: the tracker-forecast map as an observation (csrc/tracks/libd2d_tracks.so, its own version) ----
+D2D_TRACKS_VERSION = 1
+TRACKS_MAX_SAMPLES = 255
+TRACKS_POINTERS = ('trk_radius', 'win', 'cells', 'last_step')
+TRACKS_BUFFERS = ('win', 'cells', 'last_step')               # per env, the channel's own; `trk_radius` is the device planner's
+
+
+class Tracks(C.Structure):
+    """include/d2d_tracks.h `d2d_tracks`."""
+    _fields_ = [(n, C.c_void_p) for n in TRACKS_POINTERS] + [('margin', C.c_double), ('samples', C.c_int32), ('force', C.c_int32)]
+
+
+def bind_tracks(lib):
+    """argtypes / restypes of include/d2d_tracks.h on a loaded CDLL."""
+    P = C.POINTER
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'update': (C.c_int, [P(Cfg), P(State), P(Tracks), C.c_void_p]),
+    }
+    return _bind(lib, 'd2d_tracks_', sig)

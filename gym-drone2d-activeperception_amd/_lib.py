@@ -14,6 +14,7 @@ JERK_LIB_PATH = os.path.join(_HERE, 'csrc', 'jerk', 'libd2d_jerk.so')           
 GAZE_LIB_PATH = os.path.join(_HERE, 'csrc', 'gaze', 'libd2d_gaze.so')                   # include/d2d_gaze.h
 SEEN_LIB_PATH = os.path.join(_HERE, 'csrc', 'seen', 'libd2d_seen.so')                   # include/d2d_seen.h
 SCAN_LIB_PATH = os.path.join(_HERE, 'csrc', 'scan', 'libd2d_scan.so')                   # include/d2d_scan.h
+TRACKS_LIB_PATH = os.path.join(_HERE, 'csrc', 'tracks', 'libd2d_tracks.so')             # include/d2d_tracks.h
 
 
 class D2DError(RuntimeError):
@@ -41,6 +42,7 @@ _LIBRARIES = {
     'libd2d_gaze.so': (A.bind_gaze, 'version', 'D2D_GAZE_VERSION', 'version', 'gaze/build.sh'),
     'libd2d_seen.so': (A.bind_seen, 'version', 'D2D_SEEN_VERSION', 'version', 'seen/build.sh'),
     'libd2d_scan.so': (A.bind_scan, 'version', 'D2D_SCAN_VERSION', 'version', 'scan/build.sh'),
+    'libd2d_tracks.so': (A.bind_tracks, 'version', 'D2D_TRACKS_VERSION', 'version', 'tracks/build.sh'),
 }
 
 
@@ -99,6 +101,11 @@ def load_scan_library(path=SCAN_LIB_PATH):
     return _load('libd2d_scan.so', path)
 
 
+def load_tracks_library(path=TRACKS_LIB_PATH):
+    """The tracker-forecast map as an observation channel, a library of its own (include/d2d_tracks.h)."""
+    return _load('libd2d_tracks.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -131,6 +138,7 @@ class HipBackend:
     supports_rvo_live = True              # include/d2d_rvo_live.h: the RVO launches that leave finished envs alone (run_episodes)
     supports_seen_obs = True              # include/d2d_seen.h: the time-since-observed map and its crop (VecDrone2DEnv(..., seen_obs=True))
     supports_scan_obs = True              # include/d2d_scan.h: the per-ray scan of the raycast (VecDrone2DEnv(..., scan_obs=True))
+    supports_tracks_obs = True            # include/d2d_tracks.h: the tracker-forecast map's window (VecDrone2DEnv(..., tracks_obs=True))
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -150,6 +158,7 @@ class HipBackend:
         self.glib = self.gfn = None       # libd2d_gaze.so: loaded by the first gaze call of the step path, likewise
         self.olib = self.ofn = None       # libd2d_seen.so: loaded by the first update of the time-since-observed map, likewise
         self.ylib = self.yfn = None       # libd2d_scan.so: loaded by the first update of the per-ray scan, likewise
+        self.tlib = self.tfn = None       # libd2d_tracks.so: loaded by the first update of the tracker-forecast map, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -441,6 +450,13 @@ class HipBackend:
         if self.yfn is None:
             self.ylib, self.yfn = load_scan_library()
         _check(self.yfn['update'](C.byref(cfg), C.byref(st), C.byref(scan), self._stream()), self.yfn, 'd2d_scan')
+
+    def tracks_update(self, cfg, st, tracks):
+        """d2d_tracks_update: `tracks` is an _abi.Tracks of device pointers (VecDrone2DEnv(..., tracks_obs=True)); the envs whose step
+        counter differs from that of their latest update (all of them with `force`) get the window of the tracker-forecast map"""
+        if self.tfn is None:
+            self.tlib, self.tfn = load_tracks_library()
+        _check(self.tfn['update'](C.byref(cfg), C.byref(st), C.byref(tracks), self._stream()), self.tfn, 'd2d_tracks')
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -170,6 +170,7 @@ class ActionStream:
         b.stream_restore(items, n, self.refill)
         env.reset_plugins(self.refill)
         env._seen_update()                     # a refilled slot's call 1 (its records are zero); every other slot's call has not moved
+        env._tracks_update()                   # a refilled slot's counter jumped back and it has no active tracker: a zero window
         return True
 
     # ------------------------------------------------------------------ the surface
@@ -177,7 +178,7 @@ class ActionStream:
         """`actions`: [B] float64 on the env's device, in [-1, 1] as VecDrone2DEnv.step takes them.  Returns (obs, terms, done, info):
         `obs` the dict of step() as views; `terms` device tensors [B]: newly_tracked, explored (this step's increase of the slot's
         discovered cells; the first step of a fresh world counts from 0), collision (0 none, 1 static, 2 dynamic: the flags byte of
-        the CSV row), goal, dead_lock, freezing, with seen_obs refreshed (VecDrone2DEnv.refreshed); `done` [B] bool; `info`: live (the slot played an episode in this step), episode
+        the CSV row), goal, dead_lock, freezing, with seen_obs refreshed (VecDrone2DEnv.refreshed), with tracks_obs track_cells (VecDrone2DEnv.track_cells); `done` [B] bool; `info`: live (the slot played an episode in this step), episode
         (int32, the episode it played, -1 once retired), steps (the slot's step counter).  Everything but `done` is a view that the
         next call overwrites."""
         env, s = self.env, self.env.state
@@ -212,6 +213,8 @@ class ActionStream:
                  'dead_lock': s.flags[:, A.F_DEADLOCK], 'freezing': s.flags[:, A.F_FREEZING]}
         if env.seen is not None:               # the cells the slot's pose newly covered (include/d2d_seen.h)
             terms['refreshed'] = env.seen['refreshed']
+        if env.tracks is not None:             # the cells of the slot's window a tracker's forecast reaches (include/d2d_tracks.h)
+            terms['track_cells'] = env.tracks['cells']
         info = {'live': self.live, 'episode': self.slot_episode, 'steps': s.counters[:, A.C_STEPS]}
         return obs, terms, done, info
 

@@ -252,7 +252,7 @@ def _grid_tile(params, backend, grid_layout):
 class VecDrone2DEnv:
     def __init__(self, params, num_envs, device='cuda:0', planner=None, env_offset=0, backend=None,
                  kf_enabled=True, worlds=None, device_plugins=False, gaze=None, grid_layout=None, jerk_tie=None, redraw_agents=False,
-                 swept_obs=False, seen_obs=False, scan_obs=False):
+                 swept_obs=False, seen_obs=False, scan_obs=False, tracks_obs=False, tracks_samples=31, tracks_margin=None):
         """`jerk_tie`: (tie_perm, tie_eq) for planner='Jerk_Primitive' in place of the table of this host's np.argsort
         (jerk_plugin.tie_table): a recorded episode replays with the table of the numpy that recorded it.
         `redraw_agents`: the worlds this env builds itself (worlds=None, worlds='device') are those of the validation study: every
@@ -271,7 +271,14 @@ class VecDrone2DEnv:
         raycast (include/d2d_scan.h); `ray_end`, `ray_kind` and `ray_hits` hold what the reference keeps as env.drone.rays
         (utils.py:712, :746), bit for bit but for 'wall' at a range stop, which is 2 where the reference has the raw map_gt value (2,
         or 3 on a cell that still carries the previous step's dynamic mark).  A copy of the pose in front of every single step and
-        one more launch behind it; no rays before the first step; closed_loop(n > 1) and rollout() refuse it."""
+        one more launch behind it; no rays before the first step; closed_loop(n > 1) and rollout() refuse it.
+        `tracks_obs`: obs['track_map'] [B, 1, L, L] float32 is the window around the drone of the tracker-forecast map
+        (include/d2d_tracks.h): 1 + the first of the samples k = 0 .. tracks_samples - 1 (1 .. 255; 31 is k * dt up to 3 s, Oxford's
+        tau_s, yaw_planner.py:55) at which an active Kalman tracker's estimate_pos(k * dt) comes within drone_radius +
+        tracker.radius + tracks_margin of the cell's centre, 0 where none does.  `tracks_margin` None is 5 + var_cam, the keep-out
+        of Planner.is_free (traj_planner.py:57); 0 is the test of replan_check (:227).  `track_win` and `track_cells` hold the
+        uint8 window and its nonzero cells.  The radii are the device planner's (planner 'Primitive' or 'Jerk_Primitive' with
+        device_plugins=True).  One more launch behind every single step and reset(); closed_loop() and rollout() refuse it."""
         self.params = with_defaults(params)
         self.redraw_agents = bool(redraw_agents)
         self.num_envs = int(num_envs)
@@ -428,6 +435,10 @@ class VecDrone2DEnv:
         self.scan = None                   # the buffers of include/d2d_scan.h
         if self.scan_obs:
             self._init_scan()
+        self.tracks_obs = bool(tracks_obs)
+        self.tracks = None                 # the buffers of include/d2d_tracks.h
+        if self.tracks_obs:
+            self._init_tracks(planner, kf_enabled, tracks_samples, tracks_margin)
 
     def _init_swept(self, planner):
         """The refusals and the buffers of swept_obs=True"""
@@ -609,6 +620,67 @@ class VecDrone2DEnv:
         bits = (h.unsqueeze(-1) >> torch.arange(32, dtype=torch.int32, device=h.device)) & 1
         return bits.reshape(h.shape[0], h.shape[1], -1)[:, :, :self.cfg.N].bool()
 
+    def _init_tracks(self, planner, kf_enabled, samples, margin):
+        """The refusals and the buffers of tracks_obs=True, and the first update: a fresh world has no active tracker (utils.py:182)"""
+        if not 1 <= int(samples) <= A.TRACKS_MAX_SAMPLES:
+            raise ValueError(f'tracks_obs=True: tracks_samples={samples!r} (1 .. {A.TRACKS_MAX_SAMPLES}: the window holds 1 + the sample '
+                             'as a uint8)')
+        if not kf_enabled:
+            raise ValueError('tracks_obs=True reads the Kalman trackers (kf_enabled=True)')
+        radii = self.jerk.t['trk_radius'] if self.jerk is not None else \
+            self.plugins.t['trk_radius'] if self.plugins is not None and self.plugins.planner == A.PLAN_PRIMITIVE else None
+        if radii is None:
+            raise NotImplementedError(f"tracks_obs=True: planner {planner!r} {'with' if self.plugins is not None else 'without'} device "
+                                      'plugins keeps no tracker radii (trk_radius, envs/drone_v2.py:46, utils.py:239: the device '
+                                      "planners' d2d_plan.trk_radius / d2d_jerk_call.trk_radius); build the env with planner='Primitive' "
+                                      "or 'Jerk_Primitive' and device_plugins=True")
+        backend_for(self.backend, None, 'supports_tracks_obs', 'has no tracker-forecast launch (include/d2d_tracks.h: d2d_tracks_update): '
+                    'tracks_obs=True runs on the HIP backend, with csrc/tracks/libd2d_tracks.so built')
+        B, L, dev = self.num_envs, self.cfg.L, self.device
+        self.tracks = dict(trk_radius=radii, win=torch.zeros((B, L, L), dtype=torch.uint8, device=dev),
+                           cells=torch.zeros(B, dtype=torch.int32, device=dev), last_step=torch.full((B,), -1, dtype=torch.int32, device=dev),
+                           obs=torch.zeros((B, L, L), dtype=torch.float32, device=dev))
+        self._tracks = A.Tracks()
+        for n in A.TRACKS_POINTERS:
+            t = self.tracks[n]
+            setattr(self._tracks, n, t.data_ptr() if t.numel() else self.state._dummy.data_ptr())
+        self._tracks.margin = float(5 + self.params.var_cam if margin is None else margin)
+        self._tracks.samples, self._tracks.force = int(samples), 0
+        self._tracks_update()
+
+    def _tracks_update(self):
+        """d2d_tracks_update: every env whose step counter differs from that of its latest update gets its window; a finished env,
+        whose counter stands still, is left as it is, and a reset or refilled slot, which has no active tracker, comes out zero"""
+        if self.tracks is not None and self.num_envs:
+            self.backend.tracks_update(self.cfg, self._st, self._tracks)
+            self.tracks['obs'].copy_(self.tracks['win'])       # obs['track_map']: the same values as float32, resident
+
+    def tracks_refresh(self):
+        """The window of every env from the state as it stands, whatever the step counters say: for a caller that writes the drone,
+        the trackers or the radii itself"""
+        self._tracks_needed('tracks_refresh()')
+        self._tracks.force = 1
+        try:
+            self._tracks_update()
+        finally:
+            self._tracks.force = 0
+
+    def _tracks_needed(self, what):
+        if not self.tracks_obs:
+            raise RuntimeError(f'{what}: build the env with tracks_obs=True')
+
+    @property
+    def track_win(self):
+        """[B, L, L] uint8: the window of the tracker-forecast map, 1 + the first sample that reaches the cell, 0 = none"""
+        self._tracks_needed('track_win')
+        return self.tracks['win']
+
+    @property
+    def track_cells(self):
+        """[B] int32: the nonzero cells of each env's window"""
+        self._tracks_needed('track_cells')
+        return self.tracks['cells']
+
     # ------------------------------------------------------------------ gym-like surface (batched)
     @property
     def N(self):
@@ -629,6 +701,7 @@ class VecDrone2DEnv:
         self._swept_zero(mask)
         self._seen_zero(mask)
         self._scan_zero(mask)
+        self._tracks_update()              # (a reset env's counter jumped back: its window comes out zero)
         return {}
 
     def _rvo_agents(self):
@@ -666,6 +739,7 @@ class VecDrone2DEnv:
             self.backend.step(self.cfg, self._st)
         self._seen_update()
         self._scan_update()
+        self._tracks_update()
 
     def run_gaze(self):
         """d2d_gaze_act for every env that is not done: the action of the coming step, from what the previous step left.  The
@@ -727,6 +801,7 @@ class VecDrone2DEnv:
                 self.backend.swept_crop(self.cfg, self._st, self._swept)
             self._seen_update()
             self._scan_update()
+            self._tracks_update()
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -813,6 +888,7 @@ class VecDrone2DEnv:
             self.backend.run_stages(self.cfg, self._st, A.ST_ACT | A.ST_SKIP_DONE)
             self._seen_update()
             self._scan_update()
+            self._tracks_update()
             self._advance_noise(1)
         finally:
             if noise is not None:
@@ -893,6 +969,7 @@ class VecDrone2DEnv:
         self._set_action(actions)
         self.backend.act(self.cfg, self._st)
         self._seen_update()
+        self._tracks_update()
         return self._result()
 
     def rollout(self, actions, pin=None, collisions=False, streams=1):
@@ -908,6 +985,10 @@ class VecDrone2DEnv:
         if self.scan is not None:
             raise NotImplementedError('rollout(): scan_obs=True does not run inside a fused rollout (the rays of its steps would be gone: '
                                       'the launch of include/d2d_scan.h follows every single step, from the pose in front of it); step '
+                                      'the env with step() / action_stream() / policy_step() / run_episodes()')
+        if self.tracks is not None:
+            raise NotImplementedError('rollout(): tracks_obs=True does not run inside a fused rollout (its steps would go unseen by the '
+                                      'tracker-forecast map, whose launch of include/d2d_tracks.h follows every single step); step '
                                       'the env with step() / action_stream() / policy_step() / run_episodes()')
         actions = torch.as_tensor(actions, dtype=torch.float64, device=self.device).contiguous()
         T = actions.shape[0]
@@ -992,6 +1073,8 @@ class VecDrone2DEnv:
             obs['age_map'] = self.seen['obs'].unsqueeze(1)
         if self.scan is not None:              # one range and one outcome per ray of the latest step's raycast
             obs['scan'] = self.scan['obs']
+        if self.tracks is not None:            # the window of the tracker-forecast map, as float32
+            obs['track_map'] = self.tracks['obs'].unsqueeze(1)
         done = s.flags[:, A.F_DONE].bool()
         info = {'collision_flag': s.flags[:, A.F_COLLISION], 'dead_lock_flag': s.flags[:, A.F_DEADLOCK],
                 'freezing_flag': s.flags[:, A.F_FREEZING], 'state_machine': s.counters[:, A.C_SM],
@@ -1125,7 +1208,7 @@ class VecDrone2DEnv:
         the step sequences of run_episodes() elsewhere -- and with swept_obs, whose map exists only between two stages of a step.
         With seen_obs, whose launch follows every single step, `n` times the path taken for n = 1"""
         if self.plugins is not None and not self.rvo and self.swept is None:
-            if self.seen is None and self.scan is None:
+            if self.seen is None and self.scan is None and self.tracks is None:
                 self.closed_loop(n, freeze_done=True)
                 return
             for _ in range(n):             # the persistent launch, one step at a time
@@ -1133,6 +1216,7 @@ class VecDrone2DEnv:
                 self._closed_loop_steps(1, A.DONE_FREEZE)
                 self._seen_update()
                 self._scan_update()
+                self._tracks_update()
         elif self.plugins is not None:
             for _ in range(n):
                 self._plugins_step()
@@ -1170,6 +1254,7 @@ class VecDrone2DEnv:
         self.reset_plugins(refill)
         self._seen_zero(refill)
         self._scan_zero(refill)
+        self._tracks_update()              # (a refilled slot's counter jumped back: its window comes out zero)
 
     def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
         """Episodes map_id + 0 .. map_id + num_episodes - 1 over the env's `num_envs` slots: a slot whose episode has ended is
@@ -1311,6 +1396,10 @@ class VecDrone2DEnv:
         if self.seen is not None:
             raise NotImplementedError('closed_loop(): seen_obs=True does not run inside the persistent closed loop (its steps would go '
                                       'unseen by the time-since-observed map, whose launch of include/d2d_seen.h follows every single '
+                                      'step); step the env with action_stream() / policy_step() / run_episodes()')
+        if self.tracks is not None:
+            raise NotImplementedError('closed_loop(): tracks_obs=True does not run inside the persistent closed loop (its steps would go '
+                                      'unseen by the tracker-forecast map, whose launch of include/d2d_tracks.h follows every single '
                                       'step); step the env with action_stream() / policy_step() / run_episodes()')
         if self.scan is not None and (int(nsteps) > 1 or auto_reset):
             raise NotImplementedError('closed_loop(): scan_obs=True takes one step a call and no auto_reset (inside the persistent loop the '

@@ -1,7 +1,7 @@
 #!/bin/bash
 # sha256 of the device code object (gfx950 ELF, no host code) that a library's build.sh makes of a tree's .hip source.  Two trees
 # whose kernels are the same print the same value: the check for a change that is meant to touch host code or dead code only.
-#   tools/device_code_sha.sh [TREE [hip|worlds|metrics|rvo|jerk|gaze|seen|scan]] (default: this tree, e.g. a `git worktree` of the parent commit;
+#   tools/device_code_sha.sh [TREE [hip|worlds|metrics|rvo|jerk|gaze|seen|scan|tracks]] (default: this tree, e.g. a `git worktree` of the parent commit;
 #                                                                      hip = csrc/build.sh, the others csrc/<name>/build.sh)
 #   D2D_EXTRA_FLAGS=-DD2D_GAZE_EXACT_ONLY tools/device_code_sha.sh    (the libd2d_hip_exact.so build)
 # -cuid pins the one symbol (__hip_cuid_<hash>) that otherwise differs from build to build.
@@ -9,8 +9,8 @@ set -euo pipefail
 TREE=$(cd "${1:-$(dirname "$0")/..}" && pwd)
 case "${2:-hip}" in
   hip) BUILD=build.sh ;;
-  worlds | metrics | rvo | jerk | gaze | seen | scan) BUILD=$2/build.sh ;;
-  *) echo "$0: library '$2': hip, worlds, metrics, rvo, jerk, gaze, seen or scan" >&2; exit 2 ;;
+  worlds | metrics | rvo | jerk | gaze | seen | scan | tracks) BUILD=$2/build.sh ;;
+  *) echo "$0: library '$2': hip, worlds, metrics, rvo, jerk, gaze, seen, scan or tracks" >&2; exit 2 ;;
 esac
 TMP=$(mktemp -d)
 trap 'rm -rf "$TMP"' EXIT
