@@ -9,6 +9,8 @@ Layout
   state.py       device-resident batch state
   vec_env.py     VecDrone2DEnv: B envs stepped in lock-step on one GPU
   action_stream.py  ActionStream: seeded episodes over resident slots, stepped with the caller's gaze actions (VecDrone2DEnv.action_stream)
+  fork.py        slot forks: the per-slot tensors of an env, the checks and the one launch of VecDrone2DEnv.load_slots / fork (include/d2d_fork.h)
+  whatif.py      branch_terms: K gaze actions tried from every slot's present state in a scratch env
   env.py         Drone2DEnv2: single-env gym facade (gym-2d-perception-v2) over VecDrone2DEnv
   planners.py    --planner plugin surface (traj_planner.py): Primitive / NoMove = views of the device stages
   gaze.py        --gaze_method plugin surface (yaw_planner.py): Oxford = the device stage, NoControl, Rotating

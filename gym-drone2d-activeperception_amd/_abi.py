@@ -417,3 +417,25 @@ def bind_tracks(lib):
         'update': (C.c_int, [P(Cfg), P(State), P(Tracks), C.c_void_p]),
     }
     return _bind(lib, 'd2d_tracks_', sig)
+
+
+# ---- include/d2d_fork.h: whole slot states copied between envs or inside one (csrc/fork/libd2d_fork.so, its own version) ----
+D2D_FORK_VERSION = 1
+FORK_MAX_ITEMS, FORK_PARTS, FORK_SMALL_BYTES = 64, 8, 4096
+FORK_LEFT, FORK_COPIED, FORK_REFUSED = 0, 1, 2
+
+
+class ForkItem(C.Structure):
+    """include/d2d_fork.h `d2d_fork_item`."""
+    _fields_ = [('dst', C.c_void_p), ('src', C.c_void_p)] + [(n, C.c_int64) for n in ('dst_stride', 'src_stride', 'bytes')]
+
+
+def bind_fork(lib):
+    """argtypes / restypes of include/d2d_fork.h on a loaded CDLL."""
+    V, I = C.c_void_p, C.c_int32
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'slots': (C.c_int, [V, I, V, I, I, I, V, V]),
+    }
+    return _bind(lib, 'd2d_fork_', sig)

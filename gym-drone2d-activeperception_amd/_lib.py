@@ -15,6 +15,7 @@ GAZE_LIB_PATH = os.path.join(_HERE, 'csrc', 'gaze', 'libd2d_gaze.so')           
 SEEN_LIB_PATH = os.path.join(_HERE, 'csrc', 'seen', 'libd2d_seen.so')                   # include/d2d_seen.h
 SCAN_LIB_PATH = os.path.join(_HERE, 'csrc', 'scan', 'libd2d_scan.so')                   # include/d2d_scan.h
 TRACKS_LIB_PATH = os.path.join(_HERE, 'csrc', 'tracks', 'libd2d_tracks.so')             # include/d2d_tracks.h
+FORK_LIB_PATH = os.path.join(_HERE, 'csrc', 'fork', 'libd2d_fork.so')                   # include/d2d_fork.h
 
 
 class D2DError(RuntimeError):
@@ -43,6 +44,7 @@ _LIBRARIES = {
     'libd2d_seen.so': (A.bind_seen, 'version', 'D2D_SEEN_VERSION', 'version', 'seen/build.sh'),
     'libd2d_scan.so': (A.bind_scan, 'version', 'D2D_SCAN_VERSION', 'version', 'scan/build.sh'),
     'libd2d_tracks.so': (A.bind_tracks, 'version', 'D2D_TRACKS_VERSION', 'version', 'tracks/build.sh'),
+    'libd2d_fork.so': (A.bind_fork, 'version', 'D2D_FORK_VERSION', 'version', 'fork/build.sh'),
 }
 
 
@@ -106,6 +108,11 @@ def load_tracks_library(path=TRACKS_LIB_PATH):
     return _load('libd2d_tracks.so', path)
 
 
+def load_fork_library(path=FORK_LIB_PATH):
+    """The slot fork, a library of its own (include/d2d_fork.h)."""
+    return _load('libd2d_fork.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -139,6 +146,7 @@ class HipBackend:
     supports_seen_obs = True              # include/d2d_seen.h: the time-since-observed map and its crop (VecDrone2DEnv(..., seen_obs=True))
     supports_scan_obs = True              # include/d2d_scan.h: the per-ray scan of the raycast (VecDrone2DEnv(..., scan_obs=True))
     supports_tracks_obs = True            # include/d2d_tracks.h: the tracker-forecast map's window (VecDrone2DEnv(..., tracks_obs=True))
+    supports_fork = True                  # include/d2d_fork.h: whole slot states copied in one launch (load_slots, fork, whatif.branch_terms)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -159,6 +167,7 @@ class HipBackend:
         self.olib = self.ofn = None       # libd2d_seen.so: loaded by the first update of the time-since-observed map, likewise
         self.ylib = self.yfn = None       # libd2d_scan.so: loaded by the first update of the per-ray scan, likewise
         self.tlib = self.tfn = None       # libd2d_tracks.so: loaded by the first update of the tracker-forecast map, likewise
+        self.klib = self.kfn = None       # libd2d_fork.so: loaded by the first fork of slots, likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -457,6 +466,15 @@ class HipBackend:
         if self.tfn is None:
             self.tlib, self.tfn = load_tracks_library()
         _check(self.tfn['update'](C.byref(cfg), C.byref(st), C.byref(tracks), self._stream()), self.tfn, 'd2d_tracks')
+
+    def fork_slots(self, items, n_items, src_of, B_src, in_place, status):
+        """d2d_fork_slots: `items` is a device tensor that holds n_items packed _abi.ForkItem records (fork.pack_items); slot e of the
+        destination buffers becomes slot src_of[e] ([B_dst] int32) of the source buffers ([B_src] slots), status [B_dst] uint8 says
+        what happened to it (FORK_LEFT / FORK_COPIED / FORK_REFUSED).  No host read"""
+        if self.kfn is None:
+            self.klib, self.kfn = load_fork_library()
+        _check(self.kfn['slots'](items.data_ptr() if n_items else None, int(n_items), src_of.data_ptr(), src_of.shape[0], int(B_src),
+                                 int(bool(in_place)), status.data_ptr(), self._stream()), self.kfn, 'd2d_fork')
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -135,6 +135,7 @@ class ActionStream:
             torch.eq(s.flags[:, A.F_DONE], 0, out=self.live)
         self.finished = self.counts[1]
         self.items = restore_items(env, self._prev)
+        env._action_stream = self              # (load_slots() into an env with an open stream is refused)
 
     # ------------------------------------------------------------------ the turn
     def _item_array(self):
@@ -233,4 +234,5 @@ class ActionStream:
         self.env.sync()
         self.closed = True
         self.env._stream_keep = None
+        self.env._action_stream = None
         self._packed = {}

@@ -280,6 +280,12 @@ class VecDrone2DEnv:
         uint8 window and its nonzero cells.  The radii are the device planner's (planner 'Primitive' or 'Jerk_Primitive' with
         device_plugins=True).  One more launch behind every single step and reset(); closed_loop() and rollout() refuse it."""
         self.params = with_defaults(params)
+        # the arguments as given: sibling() builds a second env from them
+        self._ctor = dict(params=params, device=device, planner=planner, env_offset=env_offset, backend=backend, kf_enabled=kf_enabled,
+                          worlds=worlds, device_plugins=device_plugins, gaze=gaze, grid_layout=grid_layout, jerk_tie=jerk_tie,
+                          redraw_agents=redraw_agents, swept_obs=swept_obs, seen_obs=seen_obs, scan_obs=scan_obs, tracks_obs=tracks_obs,
+                          tracks_samples=tracks_samples, tracks_margin=tracks_margin)
+        self._action_stream = None         # the open action_stream.ActionStream over this env, or None
         self.redraw_agents = bool(redraw_agents)
         self.num_envs = int(num_envs)
         self.env_offset = int(env_offset)
@@ -1435,6 +1441,54 @@ class VecDrone2DEnv:
 
     def sync(self):
         self.backend.sync()
+
+    # ------------------------------------------------------------------ slot forks (include/d2d_fork.h, fork.py)
+    def fork_items(self, src_env=None):
+        """[(name, dst tensor, src tensor)] of every per-slot tensor a slot's future depends on or a caller can read, `dst` this env's
+        and `src` that of `src_env` (default: this env): all of state.t (the noise stream, the pillars and under RVO both halves of
+        the velocity swap, by the names they stand for now), plugins.t but for the launch arguments, jerk.t, both trk_radius0, the
+        gaze state and the dicts of the four observation channels.  What is not listed, and why, is fork.EXCLUDED; the reset
+        snapshot (init_state) is not a holder: reset() refuses after a load.  A loop over `.cpu()` of it saves a batch to the host."""
+        from . import fork
+        return fork.items_of(self, self if src_env is None else src_env)
+
+    def load_slots(self, src_env, src_of):
+        """Slot e of this env becomes slot src_of[e] of `src_env`, in everything fork_items() lists, by one launch and without a
+        host read (d2d_fork_slots).  `src_of`: [num_envs] int32 on the device; -1 leaves the slot alone.  Returns `status`
+        [num_envs] uint8 on the device: FORK_LEFT 0, FORK_COPIED 1, FORK_REFUSED 2 (src_of[e] >= src_env.num_envs).
+
+        The two envs are the same in everything but the number of slots -- every cfg field but B, planner, device_plugins, gaze,
+        motion profile, observation channels, and so the names and rows of their items -- or the call raises a ValueError that names
+        the field; sibling() builds such an env.  Neither has set_noise() rows installed, and this env has no open action_stream();
+        the SOURCE may have one, it is only read: that is the what-if from a live stream (whatif.branch_terms).  Afterwards this env
+        has played other worlds than its snapshot: reset() and closed_loop(auto_reset=True) refuse, as after a stream."""
+        from . import fork
+        return fork.load_slots(self, src_env, src_of, in_place=src_env is self)
+
+    def fork(self, src_of):
+        """load_slots(self, src_of): slot e becomes slot src_of[e] of this same env.  A slot may be read only if it is not written
+        in the same launch: slot e with s = src_of[e] != e is copied only when src_of[s] < 0 or src_of[s] == s, and is refused
+        otherwise (status 2, nothing of it written) -- so `src_of = [0, 0, 0, 0]` fans slot 0 out, and a permutation is refused slot
+        by slot.  The rule reads src_of alone, so the result depends on no order; src_of[e] == e or < 0 leaves slot e alone."""
+        return self.load_slots(self, src_of)
+
+    def sibling(self, num_envs, backend=None):
+        """A second env of `num_envs` slots built with the arguments this one was built with, the backend included (`backend`: another
+        one, for backends that serve one env each): what load_slots() loads branches into.  Worlds that were handed over are handed
+        on, repeated or cut to `num_envs`; the slots' first contents matter to nobody who loads them."""
+        a = dict(self._ctor)
+        w, n = a['worlds'], int(num_envs)
+        if isinstance(w, DeviceWorlds):
+            idx = torch.arange(n, device=w.state.device) % max(w.num_envs, 1)
+            a['worlds'] = w.spread(idx if w.index is None else w.index.to(idx.device)[idx])
+        elif isinstance(w, (list, tuple)):
+            a['worlds'] = [w[i % len(w)] for i in range(n)] if w else w
+        if backend is not None:
+            a['backend'] = backend
+        elif a['backend'] is None:
+            a['backend'] = self.backend
+        params = a.pop('params')
+        return type(self)(params, n, **a)
 
     # ------------------------------------------------------------------ episode statistics (CSV row, experiment.py:73-103)
     def episode_stats(self):
