@@ -439,3 +439,50 @@ def bind_fork(lib):
         'slots': (C.c_int, [V, I, V, I, I, I, V, V]),
     }
     return _bind(lib, 'd2d_fork_', sig)
+
+
+# ---- include/d2d_render.h, include/d2d_render_hooks.h: the renderer (csrc/render/libd2d_render.so, its own version) ----
+D2D_RENDER_VERSION = 1
+RK_DISC, RK_LINE, RK_ARC, RK_POLY = 1, 2, 3, 4
+RENDER_GEOM, RENDER_FIXED, RENDER_MAX_DOWNSAMPLE = 20, 10, 64
+RENDER_OK, RENDER_OVERFLOW, RENDER_BAD_SLOT = 0, 1, 2
+RENDER_ITEM_BYTES = 176
+RENDER_CALL_POINTERS = ('slots', 'pillars', 'agent_vel', 'plan_traj', 'plan_hdr', 'traj', 'traj_len', 'items', 'bbox', 'count', 'status',
+                        'frame')
+RENDER_CALL_INTS = ('S', 'P', 'K', 'plan_cap', 'cap', 'n_seeded', 'downsample', 'reserved')
+RASTER_CALL_POINTERS = ('items', 'count', 'cells', 'bbox', 'frame')
+RASTER_CALL_INTS = ('S', 'cap', 'W', 'H', 'W_px', 'H_px', 'scale', 'downsample')
+
+
+def render_cap(P, N, K):
+    """D2D_RENDER_CAP: the items of a slot with P pillars, N agents and a trajectory of at most K positions"""
+    return RENDER_FIXED + int(P) + 2 * int(N) + (int(K) - 1 if K > 1 else 0)
+
+
+class RenderItem(C.Structure):
+    """include/d2d_render.h `d2d_render_item`."""
+    _fields_ = [('kind', C.c_int32), ('rgb', C.c_uint8 * 3), ('npts', C.c_uint8), ('width', C.c_double), ('geom', C.c_double * RENDER_GEOM)]
+
+
+class RenderCall(C.Structure):
+    """include/d2d_render.h `d2d_render_call`."""
+    _fields_ = [(n, C.c_void_p) for n in RENDER_CALL_POINTERS] + [(n, C.c_int32) for n in RENDER_CALL_INTS] + \
+               [('view_range', C.c_double), ('star', C.c_double * 20)]
+
+
+class RasterCall(C.Structure):
+    """include/d2d_render_hooks.h `d2d_render_raster_call`."""
+    _fields_ = [(n, C.c_void_p) for n in RASTER_CALL_POINTERS] + [(n, C.c_int32) for n in RASTER_CALL_INTS]
+
+
+def bind_render(lib):
+    """argtypes / restypes of include/d2d_render.h and include/d2d_render_hooks.h on a loaded CDLL."""
+    P = C.POINTER
+    sig = {
+        'version': (C.c_int, []),
+        'last_error': (C.c_char_p, []),
+        'list': (C.c_int, [P(Cfg), P(State), P(RenderCall), C.c_void_p]),
+        'frame': (C.c_int, [P(Cfg), P(State), P(RenderCall), C.c_void_p]),
+        'raster': (C.c_int, [P(RasterCall), C.c_void_p]),
+    }
+    return _bind(lib, 'd2d_render_', sig)

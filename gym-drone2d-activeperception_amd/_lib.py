@@ -16,6 +16,7 @@ SEEN_LIB_PATH = os.path.join(_HERE, 'csrc', 'seen', 'libd2d_seen.so')           
 SCAN_LIB_PATH = os.path.join(_HERE, 'csrc', 'scan', 'libd2d_scan.so')                   # include/d2d_scan.h
 TRACKS_LIB_PATH = os.path.join(_HERE, 'csrc', 'tracks', 'libd2d_tracks.so')             # include/d2d_tracks.h
 FORK_LIB_PATH = os.path.join(_HERE, 'csrc', 'fork', 'libd2d_fork.so')                   # include/d2d_fork.h
+RENDER_LIB_PATH = os.path.join(_HERE, 'csrc', 'render', 'libd2d_render.so')             # include/d2d_render.h
 
 
 class D2DError(RuntimeError):
@@ -45,6 +46,7 @@ _LIBRARIES = {
     'libd2d_scan.so': (A.bind_scan, 'version', 'D2D_SCAN_VERSION', 'version', 'scan/build.sh'),
     'libd2d_tracks.so': (A.bind_tracks, 'version', 'D2D_TRACKS_VERSION', 'version', 'tracks/build.sh'),
     'libd2d_fork.so': (A.bind_fork, 'version', 'D2D_FORK_VERSION', 'version', 'fork/build.sh'),
+    'libd2d_render.so': (A.bind_render, 'version', 'D2D_RENDER_VERSION', 'version', 'render/build.sh'),
 }
 
 
@@ -113,6 +115,11 @@ def load_fork_library(path=FORK_LIB_PATH):
     return _load('libd2d_fork.so', path)
 
 
+def load_render_library(path=RENDER_LIB_PATH):
+    """The renderer, a library of its own (include/d2d_render.h)."""
+    return _load('libd2d_render.so', path)
+
+
 def _check(rc, fn, label):
     if rc != 0:
         raise D2DError(f'{label} error {rc}: {fn["last_error"]().decode()}')
@@ -147,6 +154,7 @@ class HipBackend:
     supports_scan_obs = True              # include/d2d_scan.h: the per-ray scan of the raycast (VecDrone2DEnv(..., scan_obs=True))
     supports_tracks_obs = True            # include/d2d_tracks.h: the tracker-forecast map's window (VecDrone2DEnv(..., tracks_obs=True))
     supports_fork = True                  # include/d2d_fork.h: whole slot states copied in one launch (load_slots, fork, whatif.branch_terms)
+    supports_render = True                # include/d2d_render.h: display lists and frames of any slots (render_list, render_frames)
 
     def __init__(self, device='cuda:0'):
         import torch
@@ -168,6 +176,7 @@ class HipBackend:
         self.ylib = self.yfn = None       # libd2d_scan.so: loaded by the first update of the per-ray scan, likewise
         self.tlib = self.tfn = None       # libd2d_tracks.so: loaded by the first update of the tracker-forecast map, likewise
         self.klib = self.kfn = None       # libd2d_fork.so: loaded by the first fork of slots, likewise
+        self.vlib = self.vfn = None       # libd2d_render.so: loaded by the first render_list() / render_frames(), likewise
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -475,6 +484,23 @@ class HipBackend:
             self.klib, self.kfn = load_fork_library()
         _check(self.kfn['slots'](items.data_ptr() if n_items else None, int(n_items), src_of.data_ptr(), src_of.shape[0], int(B_src),
                                  int(bool(in_place)), status.data_ptr(), self._stream()), self.kfn, 'd2d_fork')
+
+    def _render(self, name, *args):
+        if self.vfn is None:
+            self.vlib, self.vfn = load_render_library()
+        _check(self.vfn[name](*args, self._stream()), self.vfn, 'd2d_render')
+
+    def render_list(self, cfg, st, call):
+        """d2d_render_list: `call` is an _abi.RenderCall of device pointers (VecDrone2DEnv.render_list); the display lists of its slots"""
+        self._render('list', C.byref(cfg), C.byref(st), C.byref(call))
+
+    def render_frame(self, cfg, st, call):
+        """d2d_render_frame: the frames of the call's slots from the lists render_list left in its buffers and from the drone's map"""
+        self._render('frame', C.byref(cfg), C.byref(st), C.byref(call))
+
+    def render_raster(self, call):
+        """d2d_render_raster (include/d2d_render_hooks.h): `call` is an _abi.RasterCall over a caller-made list and cell layer"""
+        self._render('raster', C.byref(call))
 
     def tan_array(self, x, out):
         self._chk(self.fn['tan_array'](x.data_ptr(), out.data_ptr(), x.numel(), self._stream()))

@@ -452,7 +452,15 @@ class Drone2DEnv2(_EnvBase):
     def render(self, mode='human'):
         """envs/drone_v2.py:263-303 is display only (pygame).  The reference's Params default to render=True and its
         Experiment.run calls env.render() every step (utils.py:75-77, experiment.py:105-106), so the default
-        invocation has to survive it: headless no-op, one warning."""
+        invocation has to survive it: headless no-op, one warning.
+        mode='rgb_array': the picture as a numpy [H, W, 3] uint8 array, drawn on the device (VecDrone2DEnv.render_frames); a host
+        planner's stored trajectory is uploaded with the call."""
+        if mode == 'rgb_array':
+            traj = None
+            if self._mode == 'host':
+                pos = getattr(getattr(self.planner, 'trajectory', None), 'positions', None)
+                traj = [np.asarray(pos if pos is not None and len(pos) else np.zeros((0, 2)), dtype=np.float64).reshape(-1, 2)]
+            return self._vec.render_frames([self._slot], trajectories=traj)[0].cpu().numpy()
         if not self._render_warned:
             import warnings
             warnings.warn('Drone2DEnv2.render(): the accelerated env is headless, render() does nothing '

@@ -196,7 +196,11 @@ class BatchState:
         vel[:, :, n_seeded:] = self.t['agents'][:, A.A_VX:A.A_VY + 1, n_seeded:]
         self.t['agent_vel'] = vel
         self.t['agent_vel_out'] = torch.zeros_like(vel)
-        pil = torch.as_tensor(np.asarray(pillars), dtype=torch.int32).reshape(B, int(n_pillars), 3)
+        self.init_pillars(pillars, n_pillars)
+
+    def init_pillars(self, pillars, n_pillars):
+        """`pillars` [B, P, 3] int32 from the worlds' obstacles (x, y, r): what RVO steers around and the renderer draws"""
+        pil = torch.as_tensor(np.asarray(pillars), dtype=torch.int32).reshape(self.cfg.B, int(n_pillars), 3)
         self.t['pillars'] = pil.to(self.device).contiguous()
 
     def clone_world(self):

@@ -352,6 +352,16 @@ class VecDrone2DEnv:
                 self.tracker_radius = None
         if self.rvo:
             self.state.init_rvo(min(int(self.params.agent_number), N), pillars, np.asarray(pillars).shape[1] if self.num_envs else self.params.pillar_number)
+        else:
+            # the pillars stay resident under either motion profile: the renderer draws them (include/d2d_render.h), and as a tensor
+            # of state.t they follow a slot through load_slots() and a stream's refill.  Host worlds built by hand that do not name
+            # theirs (or not the same number each) keep none, and none is drawn
+            if pillars is None:
+                named = [np.asarray(w['obstacles']).reshape(-1, 3) for w in worlds if 'obstacles' in w]
+                if len(named) == len(worlds) and len({len(o) for o in named}) <= 1:
+                    pillars = np.stack(named) if named else np.zeros((0, 0, 3))
+            if pillars is not None:
+                self.state.init_pillars(pillars, np.asarray(pillars).shape[1] if self.num_envs else self.params.pillar_number)
         self.init_state = self.state.clone_world()
         self._st = self.state.struct()
         self._init_st = self.init_state.struct()
@@ -1309,7 +1319,7 @@ class VecDrone2DEnv:
         N, P = self.cfg.N, inp['P']
         radius0 = self.plugins.trk_radius0 if self.plugins is not None else self.jerk.trk_radius0     # [B, max(N, 1)]: the output's shape for N > 0
         up['tracker_radius'] = radius0
-        up['obstacles'] = s.pillars if self.rvo else torch.zeros((B, P, 3), dtype=torch.int32, device=dev)
+        up['obstacles'] = s.pillars if 'pillars' in s.t and tuple(s.pillars.shape) == (B, P, 3) else torch.zeros((B, P, 3), dtype=torch.int32, device=dev)
         spec = world_spec(inp, self.cfg.grid_tile, lambda n: up[n].data_ptr() if up[n].numel() else s._dummy.data_ptr())
         slot_episode = torch.arange(B, dtype=torch.int32, device=dev)
         refill = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -1441,6 +1451,26 @@ class VecDrone2DEnv:
 
     def sync(self):
         self.backend.sync()
+
+    # ------------------------------------------------------------------ the renderer (include/d2d_render.h, render.py)
+    def render_list(self, slots=None, trajectories=None):
+        """The display list of `slots` (None: all; an int32 / int64 tensor or a list, repeats and any order allowed): the draw calls
+        of Drone2DEnv2.render behind the cell layer (envs/drone_v2.py:263-303), in its order and with its float64 numbers, as a dict
+        of device tensors -- kind [S, cap] int32 (_abi.RK_*), rgb [S, cap, 3], npts, width [S, cap], geom [S, cap, 20] float64, count
+        [S] and status [S] (RENDER_OVERFLOW: the list did not fit, count is 0).  For callers who draw vector graphics themselves.
+        Scratch of the next call; nothing is read back and nothing of the env is written."""
+        from . import render
+        return render.lists(self, slots, trajectories)
+
+    def render_frames(self, slots=None, downsample=1, out=None, trajectories=None):
+        """[S, Hf, Wf, 3] uint8 on the device: the picture Drone2DEnv2.render draws, of every slot of `slots` as it stands (a finished
+        slot: its terminal state), point-sampled at every `downsample`-th pixel of every `downsample`-th row (Hf = ceil(H_px / d),
+        Wf = ceil(W_px / d)) and rasterised by the rules of include/d2d_render.h.  `out`: a contiguous uint8 tensor with at least S
+        such rows to draw into; rows from S on are left alone.  `trajectories`: the stored trajectory's positions where a host planner
+        holds them -- a list of S arrays [n, 2], or (traj [S, K, 2] float64, traj_len [S] int32); otherwise the device Primitive
+        planner's, and none under NoMove and Jerk_Primitive.  Two launches, no host read, nothing of the env written."""
+        from . import render
+        return render.frames(self, slots, downsample, out, trajectories)
 
     # ------------------------------------------------------------------ slot forks (include/d2d_fork.h, fork.py)
     def fork_items(self, src_env=None):
