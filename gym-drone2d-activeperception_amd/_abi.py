@@ -486,3 +486,24 @@ def bind_render(lib):
         'raster': (C.c_int, [P(RasterCall), C.c_void_p]),
     }
     return _bind(lib, 'd2d_render_', sig)
+
+
+# ---- include/d2d_capture.h: the terminal frames of streamed episodes (additions to csrc/render/libd2d_render.so) ----
+RENDER_SKIPPED = 3
+CAPTURE_KIND_NAMES = ('static', 'dynamic', 'dead_lock', 'freezing', 'goal', 'other')     # D2D_CAPTURE_* 1 .. 6, in the rule's order
+CAPTURE_KINDS = len(CAPTURE_KIND_NAMES)
+CAPTURE_META_F, CAPTURE_COUNTS = 4, 3
+CAPTURE_M_EPISODE, CAPTURE_M_KIND, CAPTURE_M_STEPS, CAPTURE_M_SLOT = range(4)
+CAPTURE_ENTRY_POINTS = ('capture_select', 'render_list_sel', 'render_frame_sel')
+
+
+def bind_capture(lib):
+    """argtypes / restypes of include/d2d_capture.h on the loaded libd2d_render.so: additions to that library, looked up as optional
+    symbols (a build without them binds nothing here, and its version is the same)."""
+    P, V, I = C.POINTER, C.c_void_p, C.c_int32
+    sig = {
+        'capture_select': (C.c_int, [P(Cfg), P(State), V, C.c_uint32, I, C.c_int64, V, V, V, V, V, V]),
+        'render_list_sel': (C.c_int, [P(Cfg), P(State), P(RenderCall), V]),
+        'render_frame_sel': (C.c_int, [P(Cfg), P(State), P(RenderCall), V, C.c_int64, V]),
+    }
+    return _bind(lib, 'd2d_', sig, CAPTURE_ENTRY_POINTS)

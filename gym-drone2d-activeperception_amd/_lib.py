@@ -485,10 +485,40 @@ class HipBackend:
         _check(self.kfn['slots'](items.data_ptr() if n_items else None, int(n_items), src_of.data_ptr(), src_of.shape[0], int(B_src),
                                  int(bool(in_place)), status.data_ptr(), self._stream()), self.kfn, 'd2d_fork')
 
-    def _render(self, name, *args):
+    def _render_fn(self):
         if self.vfn is None:
             self.vlib, self.vfn = load_render_library()
-        _check(self.vfn[name](*args, self._stream()), self.vfn, 'd2d_render')
+            self.vfn = dict(self.vfn, **A.bind_capture(self.vlib))        # include/d2d_capture.h, where the build has it
+        return self.vfn
+
+    def _render(self, name, *args):
+        fn = self._render_fn()
+        if name not in fn:
+            raise D2DError(f'{RENDER_LIB_PATH} has no d2d_{name} (include/d2d_capture.h): rebuild it with csrc/render/build.sh')
+        _check(fn[name](*args, self._stream()), fn, 'd2d_render')
+
+    @property
+    def supports_capture(self):
+        """include/d2d_capture.h: the selection and the two skipping launches behind capture.Capture.  Optional symbols of
+        libd2d_render.so: true where the built library has all three"""
+        return all(n in self._render_fn() for n in A.CAPTURE_ENTRY_POINTS)
+
+    def capture_select(self, cfg, st, slot_episode, kinds, sel_slot, sel_dst, meta, pose, counts):
+        """d2d_capture_select: the finished slots of the kinds in the bit mask `kinds` that the next harvest records (slot_episode
+        None: every done slot, episode = slot) get the next rows of meta [capacity, 4] int32 and pose [capacity, 3] float64; sel_slot
+        and sel_dst [S] int32 name them for the two launches below, -1 beyond; counts [3] int64 = (taken, dropped, matched) moves on"""
+        self._render('capture_select', C.byref(cfg), C.byref(st), None if slot_episode is None else slot_episode.data_ptr(), int(kinds),
+                     sel_slot.shape[0], meta.shape[0], sel_slot.data_ptr(), sel_dst.data_ptr(), meta.data_ptr(), pose.data_ptr(),
+                     counts.data_ptr())
+
+    def render_list_sel(self, cfg, st, call):
+        """d2d_render_list_sel: render_list, an entry whose slot is -1 skipped (status RENDER_SKIPPED)"""
+        self._render('render_list_sel', C.byref(cfg), C.byref(st), C.byref(call))
+
+    def render_frame_sel(self, cfg, st, call, dst, capacity):
+        """d2d_render_frame_sel: render_frame with entry i painted into frame dst[i] ([S] int32) of call.frame [capacity, Hf, Wf, 3];
+        skipped entries and those with dst outside [0, capacity) paint nothing"""
+        self._render('render_frame_sel', C.byref(cfg), C.byref(st), C.byref(call), dst.data_ptr(), int(capacity))
 
     def render_list(self, cfg, st, call):
         """d2d_render_list: `call` is an _abi.RenderCall of device pointers (VecDrone2DEnv.render_list); the display lists of its slots"""

@@ -9,7 +9,8 @@ to be in a fresh seeded world at its next step without the host in the loop.  `s
              number stay readable, without a copy, until the caller steps again): d2d_stream_harvest, d2d_stream_assign or
              d2d_stream_assign_table, d2d_worlds_build_masked, d2d_stream_restore (include/d2d_worlds_turn.h: one launch for all that
              VecDrone2DEnv._refill_rest does with masked fills and d2d_stream_clear) and the masked resets -- all queued
-             unconditionally, nothing read back
+             unconditionally, nothing read back.  With a capture.Capture the three launches of include/d2d_capture.h go in front of
+             the harvest, here and in close(), queued as unconditionally
   actions    written for the slots that play; a slot that is done or retired keeps its action, as it keeps everything else
   one step   of the env's own episode loop with every launch leaving finished slots alone (VecDrone2DEnv._episode_steps)
   explored   d2d_stream_explored: every slot's count of discovered cells, and its increase over the previous step
@@ -109,8 +110,10 @@ class ActionStream:
     runner.record_row reads (include/d2d_worlds_stream.h D2D_STREAM_R_*), written by the turn that follows an episode's last step;
     `finished` is the device scalar of the episodes harvested so far and `finished_now()` the one method that reads it."""
 
-    def __init__(self, env, M, first, table, refill_every, max_attempts):
+    def __init__(self, env, M, first, table, refill_every, max_attempts, capture=None):
         self.env, self.num_episodes, self.refill_every = env, M, max(1, int(refill_every))
+        if capture is not None:
+            capture.check_free(env)            # (refused before anything of the env is touched; owned only once the stream stands)
         self._m0, self._table = (first, None) if table is None else (None, table)
         B, dev, s = env.num_envs, env.device, env.state
         self.rows = env.stream_rows = torch.full((M, A.STREAM_ROW_F), -1, dtype=torch.int32, device=dev)
@@ -136,6 +139,9 @@ class ActionStream:
         self.finished = self.counts[1]
         self.items = restore_items(env, self._prev)
         env._action_stream = self              # (load_slots() into an env with an open stream is refused)
+        self.capture = capture                 # capture.Capture or None: the terminal frames of the slots a harvest records
+        if capture is not None:
+            capture.attach(env, self)          # last: a constructor that raised above leaves the capture free
 
     # ------------------------------------------------------------------ the turn
     def _item_array(self):
@@ -159,6 +165,8 @@ class ActionStream:
             return False
         self._since = 0
         env, b, s = self.env, self.env.backend, self.env.state
+        if self.capture is not None:           # the finished slots as they ended, before the harvest lets them go
+            self.capture.queue(self.slot_episode)
         b.stream_harvest(env.cfg, env._st, self.slot_episode, self.rows)
         if self._table is None:
             b.stream_assign(s.flags, self.num_episodes, self._m0, self.slot_episode, self._up['map_id'], self.refill, self.counts)
@@ -230,8 +238,12 @@ class ActionStream:
         if self.closed:
             return
         if not self._idle:
+            if self.capture is not None:
+                self.capture.queue(self.slot_episode)
             self.env.backend.stream_harvest(self.env.cfg, self.env._st, self.slot_episode, self.rows)
         self.env.sync()
+        if self.capture is not None:
+            self.capture.detach(self)
         self.closed = True
         self.env._stream_keep = None
         self.env._action_stream = None

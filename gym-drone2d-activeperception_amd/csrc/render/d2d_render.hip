@@ -16,6 +16,9 @@
 //                  paint   every lane walks the kept items in order -- the box against its run first, then d2d_render_covers per
 //                          pixel -- over the 16 colours it holds in registers.  A list longer than a pass is more passes over the
 //                          same registers: order is kept, nothing is dropped.
+//   capture_select, render_list<true>, render_frame<true>   include/d2d_capture.h: one wave picks the finished slots a stream's harvest
+//                  is about to record and gives each a frame of a gallery; the list and frame kernels under SEL skip the entries
+//                  that name no slot, and a frame workgroup paints the frame its entry was given.  <false> is the text of before.
 //
 // Arithmetic is fp64 in the order include/d2d_render.h states, compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -27,6 +30,7 @@
 #define D2D_SINCOS_QUAL __device__ __forceinline__
 #define D2D_SINCOS_TBL_QUAL __device__ const
 #include "d2d_render.h"
+#include "d2d_capture.h"
 
 #define WAVE 64
 #define LIST_WAVES 4
@@ -41,6 +45,8 @@ int fail(int rc, const char *msg) {
   return rc;
 }
 
+// SEL (include/d2d_capture.h): an entry whose slot number is -1 is skipped -- the same text otherwise
+template <bool SEL>
 __global__ __launch_bounds__(LIST_WAVES *WAVE) void render_list_kernel(const d2d_cfg c, const double *__restrict__ drone,
                                                                       const double *__restrict__ agents,
                                                                       const uint8_t *__restrict__ active,
@@ -51,6 +57,13 @@ __global__ __launch_bounds__(LIST_WAVES *WAVE) void render_list_kernel(const d2d
   const long long k = (long long)blockIdx.x * LIST_WAVES + wv;
   if (k >= r.S) return;
   const int e = r.slots[k];
+  if (SEL && e == -1) {  // no slot was chosen for this entry
+    if (lane == 0) {
+      r.count[k] = 0;
+      r.status[k] = D2D_RENDER_SKIPPED;
+    }
+    return;
+  }
   if (e < 0 || e >= c.B) {  // nothing of such a slot is read
     if (lane == 0) {
       r.count[k] = 0;
@@ -129,7 +142,15 @@ struct frame_args {
   int B, cap, W, H, tile, scale, d, Wf, Hf, tiles_x, tiles_y;
 };
 
-__global__ __launch_bounds__(FRAME_LANES) void render_frame_kernel(const frame_args a) {
+// SEL (include/d2d_capture.h): list k paints frame dst[k]; a workgroup whose entry names no slot, or no frame of the gallery, is gone
+// before any LDS use or barrier -- the slot number and dst[k] are the workgroup's, so no barrier is divergent
+struct frame_sel {
+  const int32_t *dst;  // [S]
+  long long capacity;
+};
+
+template <bool SEL>
+__global__ __launch_bounds__(FRAME_LANES) void render_frame_kernel(const frame_args a, const frame_sel sel) {
   __shared__ __attribute__((aligned(16))) double krec[D2D_RENDER_LDS_ITEMS * D2D_RENDER_ITEM_F64];
   __shared__ __attribute__((aligned(8))) int16_t kbox[D2D_RENDER_LDS_ITEMS * 4];
   __shared__ int kidx[D2D_RENDER_LDS_ITEMS];
@@ -138,6 +159,12 @@ __global__ __launch_bounds__(FRAME_LANES) void render_frame_kernel(const frame_a
   const int t = threadIdx.x, lane = t & (WAVE - 1), wv = t >> 6;
   const int per = a.tiles_x * a.tiles_y;
   const int k = blockIdx.x / per, tile = blockIdx.x - k * per;
+  long long kf = k;  // the frame this workgroup paints
+  if (SEL) {
+    if (a.slots[k] == -1) return;
+    kf = sel.dst[k];
+    if (kf < 0 || kf >= sel.capacity) return;
+  }
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int tu = tx * D2D_RENDER_TILE_W, tv = ty * D2D_RENDER_TILE_H;
   const int u0 = tu + (t & 7) * D2D_RENDER_RUN, v = tv + (t >> 3);
@@ -193,7 +220,7 @@ __global__ __launch_bounds__(FRAME_LANES) void render_frame_kernel(const frame_a
   if (!mine) return;
 
   // ---- store: 48 bytes whole, or the ragged edge byte by byte ----
-  uint8_t *out = a.frame + (((size_t)k * a.Hf + v) * a.Wf + u0) * 3;
+  uint8_t *out = a.frame + (((size_t)kf * a.Hf + v) * a.Wf + u0) * 3;
   if (n == D2D_RENDER_RUN && ((uintptr_t)out & 15) == 0) {
     uint32_t w[12];
 #pragma unroll
@@ -218,6 +245,59 @@ __global__ __launch_bounds__(FRAME_LANES) void render_frame_kernel(const frame_a
   }
 }
 
+// One wave strides over the slots, 64 a pass.  The rank of a match is the carry of the passes before plus the pop-count of the
+// ballot's bits below the lane: slot order, no atomics.  The accepted ranks are a prefix (r < S and r < room), so the -1 padding
+// starts at their number.  Indices: r < S into sel_slot / sel_dst, taken + r < capacity into meta / pose, e < B into the state.
+__global__ __launch_bounds__(WAVE) void capture_select_kernel(const int B, const uint8_t *__restrict__ flags,
+                                                             const int32_t *__restrict__ counters, const double *__restrict__ drone,
+                                                             const int32_t *__restrict__ slot_episode, const uint32_t kinds, const int S,
+                                                             const long long capacity, int32_t *__restrict__ sel_slot,
+                                                             int32_t *__restrict__ sel_dst, int32_t *__restrict__ meta,
+                                                             double *__restrict__ pose, long long *counts) {
+  const int lane = threadIdx.x;
+  const long long taken = counts[0], dropped = counts[1], matched = counts[2];
+  const long long room = d2d_capture_room(taken, capacity);
+  long long carry = 0;
+  for (int base = 0; base < B; base += WAVE) {
+    const int e = base + lane;
+    bool m = false;
+    int kind = 0, ep = 0, steps = 0;
+    if (e < B) {
+      const uint8_t *f = flags + (size_t)e * 4;
+      const int32_t *c = counters + (size_t)e * D2D_CF;
+      ep = slot_episode ? slot_episode[e] : e;
+      steps = c[D2D_C_STEPS];
+      kind = d2d_capture_kind(f[D2D_F_COLLISION], f[D2D_F_DEADLOCK], f[D2D_F_FREEZING], c[D2D_C_SM]);
+      m = d2d_capture_matches(f[D2D_F_DONE], ep, steps, kind, kinds);
+    }
+    const unsigned long long ballot = __ballot(m);
+    const long long r = carry + __popcll(ballot & ((1ull << lane) - 1ull));
+    if (m && r < S && r < room) {
+      const long long row = taken + r;
+      sel_slot[r] = e;
+      sel_dst[r] = (int32_t)row;
+      int32_t *mt = meta + row * D2D_CAPTURE_META_F;
+      mt[D2D_CAPTURE_M_EPISODE] = ep;
+      mt[D2D_CAPTURE_M_KIND] = kind;
+      mt[D2D_CAPTURE_M_STEPS] = steps;
+      mt[D2D_CAPTURE_M_SLOT] = e;
+      const double *d = drone + (size_t)e * D2D_DF;
+      pose[row * 3] = d[D2D_D_X];
+      pose[row * 3 + 1] = d[D2D_D_Y];
+      pose[row * 3 + 2] = d[D2D_D_YAW];
+    }
+    carry += __popcll(ballot);
+  }
+  long long accepted = carry < S ? carry : S;
+  accepted = accepted < room ? accepted : room;
+  for (long long i = accepted + lane; i < S; i += WAVE) sel_slot[i] = sel_dst[i] = -1;
+  if (lane == 0) {  // every lane read counts before any write
+    counts[0] = taken + accepted;
+    counts[1] = dropped + (carry - accepted);
+    counts[2] = matched + carry;
+  }
+}
+
 int whole(double v, int *out) {
   if (!(v >= 1.0 && v <= 2147483647.0) || v != (double)(int)v) return 0;
   *out = (int)v;
@@ -231,12 +311,14 @@ int after_launch(const char *who) {
   return -3;
 }
 
-int run_frame(frame_args a, long long S, int W_px, int H_px, void *stream, const char *who) {
+template <bool SEL = false>
+int run_frame(frame_args a, long long S, int W_px, int H_px, void *stream, const char *who, frame_sel sel = frame_sel{nullptr, 0}) {
   a.Wf = (W_px + a.d - 1) / a.d;
   a.Hf = (H_px + a.d - 1) / a.d;
   a.tiles_x = (a.Wf + D2D_RENDER_TILE_W - 1) / D2D_RENDER_TILE_W;
   a.tiles_y = (a.Hf + D2D_RENDER_TILE_H - 1) / D2D_RENDER_TILE_H;
-  hipLaunchKernelGGL(render_frame_kernel, dim3((unsigned)(S * a.tiles_x * a.tiles_y)), dim3(FRAME_LANES), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(render_frame_kernel<SEL>, dim3((unsigned)(S * a.tiles_x * a.tiles_y)), dim3(FRAME_LANES), 0, (hipStream_t)stream, a,
+                     sel);
   return after_launch(who);
 }
 
@@ -270,14 +352,22 @@ static int check_call(const d2d_cfg *c, const d2d_state *s, const d2d_render_cal
   return 0;
 }
 
-int d2d_render_list(const d2d_cfg *c, const d2d_state *s, const d2d_render_call *r, void *stream) {
+static int run_list(const d2d_cfg *c, const d2d_state *s, const d2d_render_call *r, void *stream, const char *who, bool sel) {
   int W_px, H_px, scale;
-  const int rc = check_call(c, s, r, "d2d_render_list", &W_px, &H_px, &scale);
+  const int rc = check_call(c, s, r, who, &W_px, &H_px, &scale);
   if (rc || r->S == 0) return rc;
-  hipLaunchKernelGGL(render_list_kernel, dim3((unsigned)((r->S + LIST_WAVES - 1) / LIST_WAVES)), dim3(LIST_WAVES * WAVE), 0,
+  hipLaunchKernelGGL(sel ? render_list_kernel<true> : render_list_kernel<false>, dim3((unsigned)((r->S + LIST_WAVES - 1) / LIST_WAVES)), dim3(LIST_WAVES * WAVE), 0,
                      (hipStream_t)stream, *c, (const double *)s->drone, (const double *)s->agents, (const uint8_t *)s->active,
                      (const double *)s->target, (const int32_t *)s->counters, *r);
-  return after_launch("d2d_render_list");
+  return after_launch(who);
+}
+
+int d2d_render_list(const d2d_cfg *c, const d2d_state *s, const d2d_render_call *r, void *stream) {
+  return run_list(c, s, r, stream, "d2d_render_list", false);
+}
+
+int d2d_render_list_sel(const d2d_cfg *c, const d2d_state *s, const d2d_render_call *r, void *stream) {
+  return run_list(c, s, r, stream, "d2d_render_list_sel", true);
 }
 
 int d2d_render_frame(const d2d_cfg *c, const d2d_state *s, const d2d_render_call *r, void *stream) {
@@ -289,6 +379,37 @@ int d2d_render_frame(const d2d_cfg *c, const d2d_state *s, const d2d_render_call
   frame_args a = {r->items, r->bbox, r->count, r->slots, (const uint8_t *)s->dmap, r->frame, D2D_GRID_BYTES(c),
                   c->B, r->cap, c->W, c->H, c->grid_tile, scale, r->downsample, 0, 0, 0, 0};
   return run_frame(a, r->S, W_px, H_px, stream, "d2d_render_frame");
+}
+
+int d2d_render_frame_sel(const d2d_cfg *c, const d2d_state *s, const d2d_render_call *r, const int32_t *dst, int64_t capacity,
+                         void *stream) {
+  int W_px, H_px, scale;
+  const int rc = check_call(c, s, r, "d2d_render_frame_sel", &W_px, &H_px, &scale);
+  if (rc) return rc;
+  if (capacity < 0 || capacity > 0x7fffffffLL) return fail(-1, "d2d_render_frame_sel: 0 <= capacity < 2^31");
+  if (r->S == 0 || capacity == 0) return 0;
+  if (!r->frame || !dst) return fail(-1, "d2d_render_frame_sel: frame or dst is NULL");
+  if (c->grid_tile != 0 && c->grid_tile != 16) return fail(-1, "d2d_render_frame_sel: grid_tile is 0 or 16");
+  frame_args a = {r->items, r->bbox, r->count, r->slots, (const uint8_t *)s->dmap, r->frame, D2D_GRID_BYTES(c),
+                  c->B, r->cap, c->W, c->H, c->grid_tile, scale, r->downsample, 0, 0, 0, 0};
+  return run_frame<true>(a, r->S, W_px, H_px, stream, "d2d_render_frame_sel", frame_sel{dst, (long long)capacity});
+}
+
+int d2d_capture_select(const d2d_cfg *c, const d2d_state *s, const int32_t *slot_episode, uint32_t kinds, int32_t S, int64_t capacity,
+                       int32_t *sel_slot, int32_t *sel_dst, int32_t *meta, double *pose, int64_t *counts, void *stream) {
+  if (!c || !s) return fail(-1, "d2d_capture_select: cfg or state is NULL");
+  if (c->abi_version != D2D_ABI_VERSION) return fail(-2, "d2d_capture_select: the cfg has another D2D_ABI_VERSION");
+  if (c->B < 0 || S < 0 || capacity < 0 || capacity > 0x7fffffffLL) return fail(-1, "d2d_capture_select: B, S >= 0, 0 <= capacity < 2^31");
+  if (kinds >> D2D_CAPTURE_KINDS) return fail(-1, "d2d_capture_select: kinds has a bit beyond D2D_CAPTURE_KINDS");
+  if (!counts) return fail(-1, "d2d_capture_select: counts is NULL");
+  if (S > 0 && (!sel_slot || !sel_dst)) return fail(-1, "d2d_capture_select: sel_slot or sel_dst is NULL");
+  if (capacity > 0 && (!meta || !pose)) return fail(-1, "d2d_capture_select: meta or pose is NULL");
+  if (c->B > 0 && (!s->flags || !s->counters || !s->drone)) return fail(-1, "d2d_capture_select: flags, counters or drone is NULL");
+  if (c->B == 0 && S == 0) return 0;
+  hipLaunchKernelGGL(capture_select_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, (int)c->B, (const uint8_t *)s->flags,
+                     (const int32_t *)s->counters, (const double *)s->drone, slot_episode, kinds, (int)S, (long long)capacity, sel_slot,
+                     sel_dst, meta, pose, (long long *)counts);
+  return after_launch("d2d_capture_select");
 }
 
 int d2d_render_raster(const d2d_render_raster_call *r, void *stream) {

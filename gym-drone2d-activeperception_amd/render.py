@@ -67,9 +67,10 @@ def _ready(env, downsample):
     return d
 
 
-def call_of(env, slots, downsample=1, trajectories=None, cap=None):
+def call_of(env, slots, downsample=1, trajectories=None, cap=None, scratch=None):
     """(_abi.RenderCall, the tensors it points at) for `slots` [S] int32.  `cap`: the list capacity in place of the one derived from
-    P, N and the trajectory capacity (the tests make it too small by hand)"""
+    P, N and the trajectory capacity (the tests make it too small by hand).  `scratch`: a RenderScratch of the caller's own in place
+    of the env's (capture.Capture keeps one)"""
     d = _ready(env, downsample)
     s, S = env.state, int(slots.numel())
     traj, traj_len = _trajectories(env, trajectories, S)
@@ -79,7 +80,7 @@ def call_of(env, slots, downsample=1, trajectories=None, cap=None):
     K = int(traj.shape[1]) if traj is not None else 0
     plan_cap = int(plan['traj'].shape[1]) if plan is not None else 0
     cap = A.render_cap(P, N, max(K, plan_cap)) if cap is None else int(cap)
-    sc = env.__dict__.setdefault('_render', RenderScratch())
+    sc = scratch if scratch is not None else env.__dict__.setdefault('_render', RenderScratch())
     if sc.key != (S, cap):
         dev = env.device
         sc.items = torch.zeros((S, cap, A.RENDER_ITEM_BYTES), dtype=torch.uint8, device=dev)

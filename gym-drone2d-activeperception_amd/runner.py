@@ -278,16 +278,21 @@ class EpisodeStream:
     placed (column 0 of its record == STREAM_BUILD_FAILED, `build_failed` lists their map ids) has a row of zeros."""
 
     def __init__(self, params, num_episodes=None, slots=None, device='cuda:0', backend=None, jerk_tie=None, episodes=None,
-                 redraw_agents=False, agent_speed=None):
+                 redraw_agents=False, agent_speed=None, capture=None):
         """`episodes`: a table in place of consecutive map ids (VecDrone2DEnv.stream_episodes): a list of Params, or of (map_id,
         init_position, target_list) triples over `params`; episode k is the world of row k and `rows()` carries the row's map id,
         start and target.  The env is built from the first rows, so they are the envs as constructed.  `redraw_agents`: every world
         is that of the validation study, the agents' preferred velocities redrawn behind the construction; `agent_speed`: the rows'
-        'Agent speed' column where it is not agent_max_speed (study_row)."""
+        'Agent speed' column where it is not agent_max_speed (study_row).  `capture`: a callable env -> capture.Capture (the
+        env is built here), or None: with params.record_img set and gaze_method != 'NoControl', the reference's condition
+        (envs/training_v3.py:180-187), Capture(env, ('static', 'dynamic')).  run() saves the gallery into params.img_dir under that
+        condition and no other, whoever made the capture: a caller's capture without record_img, or under NoControl, is filled and
+        left to the caller (`self.capture`)."""
         from .vec_env import VecDrone2DEnv, build_worlds_device_of, table_params
         if slots is None or (num_episodes is None) == (episodes is None):
             raise TypeError('EpisodeStream(params, num_episodes, slots) or EpisodeStream(params, episodes=[...], slots=B)')
         p = with_defaults(params)
+        record = bool(getattr(p, 'record_img', False)) and p.gaze_method != 'NoControl'
         stepped = p.planner == 'Jerk_Primitive' or (p.planner == 'Primitive' and p.motion_profile == 'RVO')
         if stepped:
             p = SteppedExperimentBatch.accepted(p, backend)
@@ -315,6 +320,12 @@ class EpisodeStream:
         self.max_steps = int(np.ceil(p.max_flight_time / p.dt)) + 1
         self.steps_run = 0
         self.records = None
+        self.capture, self.image_paths, self._record = None, [], record
+        if capture is not None:
+            self.capture = capture(self.env)
+        elif record and int(slots):
+            from .capture import Capture
+            self.capture = Capture(self.env, ('static', 'dynamic'))
 
     @staticmethod
     def _accepted_row(ep, p):
@@ -330,8 +341,12 @@ class EpisodeStream:
                                'rows() returns its rows again, a new EpisodeStream runs the episodes again')
         if self.episodes is not None:
             kw['episodes'] = self.episodes
+        if self.capture is not None:
+            kw['capture'] = self.capture
         self.records = self.env.stream_episodes(None if self.episodes is not None else self.num_episodes, refill_every, **kw).cpu().numpy()
         self.steps_run = self.env.steps_streamed
+        if self.capture is not None and self._record:     # the reference's condition, for a capture of the caller's making too
+            self.image_paths = self.capture.save(self.params.img_dir)
         return self.rows()
 
     @property

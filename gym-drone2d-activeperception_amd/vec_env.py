@@ -1272,7 +1272,7 @@ class VecDrone2DEnv:
         self._scan_zero(refill)
         self._tracks_update()              # (a refilled slot's counter jumped back: its window comes out zero)
 
-    def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
+    def stream_episodes(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None, capture=None):
         """Episodes map_id + 0 .. map_id + num_episodes - 1 over the env's `num_envs` slots: a slot whose episode has ended is
         handed the next map id, its world is rebuilt in place on the device and everything that hangs on it is put back, so the
         slots stay full while the queue lasts and memory is bounded by the slots, not the episodes.  Returns the records
@@ -1296,8 +1296,11 @@ class VecDrone2DEnv:
         freely, and the agent radius and speed only where the derived d2d_cfg stays equal (the Kalman archive bounds take
         agent_radius); everything else is per stream, and a row that differs is refused with a ValueError that names the field and
         the row.  The first min(num_envs, len(episodes)) rows must be the envs as constructed, which runner.EpisodeStream(params,
-        episodes=...) sees to.  With `redraw_agents` every row's world is redrawn."""
-        for _ in self.stream_rounds(num_episodes, refill_every, max_attempts, trace, episodes):
+        episodes=...) sees to.  With `redraw_agents` every row's world is redrawn.
+
+        `capture`: a capture.Capture of this env -- in front of every harvest the finished slots of its kinds are drawn into its
+        gallery on the device (include/d2d_capture.h), three more launches a refill and no host read."""
+        for _ in self.stream_rounds(num_episodes, refill_every, max_attempts, trace, episodes, capture):
             pass
         return self.stream_rows
 
@@ -1331,7 +1334,7 @@ class VecDrone2DEnv:
         self._stream_keep = (up, slot_episode, refill, counts, ep)   # (the launches are asynchronous: the arrays outlive them)
         return up, ep, spec, slot_episode, refill, counts
 
-    def stream_rounds(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None):
+    def stream_rounds(self, num_episodes=None, refill_every=64, max_attempts=None, trace=None, episodes=None, capture=None):
         """stream_episodes() as a generator that hands control back after every refill that rebuilt a slot: yields (episodes finished,
         the refill bytes [B] uint8 of the round); the records so far are `stream_rows`.  For callers that look at the slots in
         between (the tests do)."""
@@ -1343,6 +1346,19 @@ class VecDrone2DEnv:
         self.steps_streamed = 0
         if M == 0 or B == 0:
             return
+        owner = object()
+        if capture is not None:
+            capture.attach(self, owner)
+        try:
+            yield from self._stream_loop(M, m0, table, every, max_attempts, trace, capture, rows)
+        finally:
+            if capture is not None:
+                capture.detach(owner)
+        self.sync()
+
+    def _stream_loop(self, M, m0, table, every, max_attempts, trace, capture, rows):
+        """the rounds of stream_rounds() for M > 0 episodes over B > 0 slots"""
+        B, s = self.num_envs, self.state
         up, ep, spec, slot_episode, refill, counts = self._stream_arrays(M, table, max_attempts)
         finished, guard = 0, (-(-M // B) + 1) * (int(np.ceil(self.params.max_flight_time / self.params.dt)) + 1 + every)
         while finished < M:
@@ -1350,6 +1366,8 @@ class VecDrone2DEnv:
                 raise RuntimeError(f'stream_episodes(): {finished} of {M} episodes after {self.steps_streamed} steps: an episode did not end')
             self._episode_steps(every)
             self.steps_streamed += every
+            if capture is not None:            # the slots the harvest is about to record, drawn as they ended
+                capture.queue(slot_episode)
             self.backend.stream_harvest(self.cfg, self._st, slot_episode, rows)
             if table is None:
                 self.backend.stream_assign(s.flags, M, m0, slot_episode, up['map_id'], refill, counts)
@@ -1367,9 +1385,8 @@ class VecDrone2DEnv:
             self.backend.build_worlds_masked(spec, self._st, refill)
             self._refill_rest(refill)
             yield finished, refill
-        self.sync()
 
-    def action_stream(self, num_episodes=None, refill_every=4, max_attempts=None, episodes=None):
+    def action_stream(self, num_episodes=None, refill_every=4, max_attempts=None, episodes=None, capture=None):
         """A stream of seeded episodes over the env's slots that the caller steps with its own gaze actions (action_stream.ActionStream):
         `stream.step(actions)` takes [B] float64 on the device and returns (obs, terms, done, info), and a slot whose episode has ended
         is in the next seeded world at the caller's next step -- harvest, assignment, masked build, d2d_stream_restore
@@ -1379,13 +1396,16 @@ class VecDrone2DEnv:
 
         Episodes, `max_attempts` and `episodes` (a table) are stream_episodes()'s.  `num_episodes=None` without a table: as many as
         the records can number, STREAM_MAX_EPISODES clipped to the map ids below 2**32 -- `rows` is allocated for all of them
-        (32 bytes an episode), so a learner that knows its budget passes it."""
+        (32 bytes an episode), so a learner that knows its budget passes it.
+
+        `capture`: a capture.Capture of this env, filled by every turn and by close() in front of their harvest (three more launches
+        each, queued unconditionally; step() still reads nothing)."""
         from .action_stream import ActionStream
         m0 = self.params.map_id + self.env_offset
         if num_episodes is None and episodes is None:
             num_episodes = max(0, min(A.STREAM_MAX_EPISODES, 2 ** 32 - m0))
         M, first = self._needs_stream(num_episodes, episodes, external=True)
-        return ActionStream(self, M, first, None if episodes is None else first, refill_every, max_attempts)
+        return ActionStream(self, M, first, None if episodes is None else first, refill_every, max_attempts, capture)
 
     def closed_loop(self, nsteps=1, auto_reset=False, freeze_done=False):
         """`nsteps` reference-style steps with the plugins on the device: a = Oxford.plan(info); perceive;
